@@ -2,12 +2,26 @@
 """Headline benchmark: decode tokens/s (+ p50 TTFT) of Qwen3-0.6B, bs=32, seq=1024, block 16,
 bf16, paged decode under hipGraph — BASELINE.json configs[1] — on N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W          # one GPU
+    python bench.py --gpus 1 --steps K --warmup W          # one GPU: the headline figure and nothing else
+    python bench.py --gpus 1 --steps K --warmup W --full   # ... plus the kernel rooflines and the CPU baseline
+    python bench.py ... --dump-outputs DIR                 # ... plus what the last timed step computed, as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W [--mode replicas|tp]
+        --master-port P bench.py --gpus N --steps K --warmup W [--full] [--mode replicas|tp|both]
+
+A plain run sets up, prefills, warms up, times `--steps` decode steps and prints the line: every figure of it comes
+from those steps themselves.  What takes runs of its own - the per-kernel rooflines (`roofline`, `chain_roofline`,
+`step_roofline.graph_replay_ms`), `cpu_baseline`, for N > 1 the tensor-parallel run beside the replicas and
+`speedup_vs_1gpu` - is measured with `--full` only.
+
+`--dump-outputs DIR` writes, after the timed steps, what a caller of the timed path holds at that point (rank 0's):
+`DIR/tokens.npy`, float32 [32, 1 + warmup + steps], the token ids step() has delivered per sequence, and
+`DIR/logits.npy`, float32 [32, vocab], the logits of the last decode step that ran inside the timed region (one GPU and
+replicas; a tensor-parallel rank holds a shard only).  Weights, prompts and sampling are seeded and greedy: the same
+arguments give the same inputs, so two builds can be compared array for array.
 
 `python bench.py --gpus N` without torchrun around it starts the N ranks itself (same command line).
-N > 1 measures BOTH ways of using N GPUs, back to back, and reports them in ONE line (--mode picks one):
+N > 1 with `--full` measures BOTH ways of using N GPUs, back to back, and reports them in ONE line (--mode picks one;
+without `--full` the default is the headline, replicas, alone):
   replicas            the headline `value`: the decode batch is a set of independent sequences, so the path shards
                       with NO data-path collective: every rank runs the whole 0.6 B model on its own GPU over its
                       own 32 sequences (global batch 32 N, weak scaling); `value` is the sum over ranks of
@@ -29,7 +43,8 @@ random.seed(0)); the 32 x 1024-token prompts are prefilled throu
 engine first (that is where p50 TTFT comes from), so the KV cache is resident in HBM
 when the timed region starts.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  Besides the contract fields it carries (roofline, chain_roofline, cpu_baseline and
+speedup_vs_1gpu with `--full` only)
   prefill_roofline  MFMA flops of one prefill step (16 x 1024 tokens: projections, causal attention, head) / the wall
                 time of the whole prefill phase (host included: first step() call -> the last step's first tokens on
                 the host; the engine queues the second step behind the first) divided by its steps, vs the 2.5 PFLOP/s
@@ -304,6 +319,24 @@ def one_gpu_reference():
     return best[0], best[1]
 
 
+DUMP_BUDGET = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """`dirname/<name>.npy`, float32; an array over its share of the budget is cut down to a fixed, seeded sample of its
+    elements (sorted flat indices, the same for every run of the same shape)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays)) - 256  # (the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` with N > 1 and no torchrun around it: start the N ranks ourselves (the same command
     line the driver uses).  On a box with fewer GPUs than ranks the ranks share devices over gloo - a functional dry
@@ -325,6 +358,10 @@ def self_launch(args) -> int:
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--mode", args.mode]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return subprocess.call(cmd, env=env)
 
 
@@ -394,6 +431,13 @@ def run_phase(args, mode: str, rank: int, world: int, port: int, model_dir: str)
         dist.barrier()
     elapsed = elapsed_local = time.perf_counter() - t0
     ctx1 = len(seqs[0])
+    if args.dump_outputs and rank == 0:
+        # what the caller holds now: the tokens step() has delivered, and the logits of the last step that ran (with
+        # lookahead the one finished and not yet consumed - the device is idle after the synchronize above)
+        arrays = {"tokens": [list(s.completion_token_ids) for s in seqs]}
+        if tp == 1:
+            arrays["logits"] = llm.model_runner.last_logits[:BATCH].float().cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     n_rep = 1
     if replicas:  # the slowest rank's clock; TTFTs of all ranks
         dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else "cpu"
@@ -469,7 +513,7 @@ def run_phase(args, mode: str, rank: int, world: int, port: int, model_dir: str)
                         "decode_graphs": sorted(mr.graphs), "lookahead": bool(getattr(llm, "lookahead", False))}
     # device time of the captured decode step alone (graph replays back to back, HIP events):
     # ms_per_step minus this is the host share of a step (scheduler, metadata, sampling, sync)
-    bucket = mr._bucket_for(BATCH) if mr.graphs else None
+    bucket = mr._bucket_for(BATCH) if mr.graphs and args.full else None
     if bucket is not None and tp == 1:  # with TP the graph holds exchanges: rank 0 must not replay it alone
         g = mr.graphs[bucket]
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -481,7 +525,7 @@ def run_phase(args, mode: str, rank: int, world: int, port: int, model_dir: str)
         e1.record()
         torch.cuda.synchronize()
         result["step_roofline"]["graph_replay_ms"] = e0.elapsed_time(e1) / 20
-    if rank == 0:
+    if rank == 0 and args.full:
         # per-GPU kernel rooflines (rank 0's shard of the heads / weights under TP): local launches, no collective
         try:
             result["roofline"] = attention_roofline(llm, seqs)
@@ -499,11 +543,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--mode", choices=("both", "replicas", "tp"), default="both",
+    ap.add_argument("--mode", choices=("both", "replicas", "tp"), default=None,
                     help="N > 1: independent replicas (weak scaling, the headline value) AND tensor parallelism at the "
-                         "fixed batch (reported under `tp_run` of the same line), or only one of the two")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "fixed batch (reported under `tp_run` of the same line), or only one of the two; default: "
+                         "both with --full, replicas without")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: kernel rooflines, graph replay time, the CPU baseline, "
+                         "for N > 1 the tensor-parallel run and the speed-up over the committed one-GPU line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the tokens delivered and the last step's logits as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.mode is None:
+        args.mode = "both" if args.full else "replicas"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
@@ -546,6 +598,8 @@ def main():
         # when it exits.  The TP phase runs under a watchdog: whatever happens to it, the line is printed.
         result = run_phase(args, "replicas", rank, world, port, model_dir) if args.mode in ("both", "replicas") else None
         tp_run = None
+        if args.mode == "both":
+            args.dump_outputs = None  # the headline run's outputs are written: the second run does not replace them
         if args.mode in ("both", "tp"):
             import threading
 
@@ -571,7 +625,7 @@ def main():
                                                             "ttft_p50_ms", "prefill_roofline", "step_roofline", "tp",
                                                             "roofline", "chain_roofline", "error") if k in tp_run}
                 result["tp_run"].setdefault("n_gpus", world)
-        if rank == 0 and result is not None:
+        if rank == 0 and result is not None and args.full:
             # north_star: ">= 6x aggregate throughput at TP = 8" - both aggregates as multiples of the one-GPU line
             ref, ref_file = one_gpu_reference()
             if ref:
@@ -585,7 +639,7 @@ def main():
                                  "not a measurement")
     if rank != 0 or result is None:
         return
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline()
     print(json.dumps(result), flush=True)
 

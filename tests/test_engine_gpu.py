@@ -706,7 +706,7 @@ def test_bench_ranks_on_one_gpu(mode, ranks):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(ranks), "--steps", "4", "--warmup", "1",
-           "--mode", mode]
+           "--mode", mode, "--full"]  # (--full: the tensor-parallel run's per-rank kernel rooflines are asserted below)
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-3000:]

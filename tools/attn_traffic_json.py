@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """profiles/rNN_attn_traffic.json from the two PMC passes of tools/final_validation.sh: measured HBM bytes per launch of
 the fused decode attention kernel (FETCH_SIZE x 2 - the gfx950 correction of MI355X_MICROARCH.md - + WRITE_SIZE, both in
-KB, separate rocprofv3 --pmc passes over `python bench.py`) against the algorithmic K/V bytes of the same launches
+KB, separate rocprofv3 --pmc passes over `python bench.py --full`) against the algorithmic K/V bytes of the same launches
 (bench.py's roofline loop: the last 560 launches of the run, bs 32, every sequence at the run's last context).
 
 usage: python tools/attn_traffic_json.py <pmc_FETCH_SIZE.txt> <pmc_WRITE_SIZE.txt> <bench_under_trace.json> <out.json>"""
@@ -28,7 +28,7 @@ def main(fetch_path, write_path, bench_path, out_path):
         "kernel": "paged_attn_decode_kernel<2,8,FUSE,PIPE,false,4> (q/k-norm + RoPE + KV store + paged attention in one launch)",
         "config": f"bs={batch}, per-sequence context {algo // (batch * 4096)}, block 16 (bench.py roofline loop: the last 560 launches of the run; "
                   f"the run's decode steps ended at context {ctx_last})",
-        "command": "tools/final_validation.sh: rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --no-cpu-baseline ; "
+        "command": "tools/final_validation.sh: rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --full --no-cpu-baseline ; "
                    "same with --pmc WRITE_SIZE (separate passes)",
         "FETCH_SIZE_kb_avg": fetch_kb, "WRITE_SIZE_kb_avg": write_kb,
         "correction": "gfx950: FETCH_SIZE counts 64 B per 128 B request on wide coalesced reads -> x2 (MI355X_MICROARCH.md, HBM)",

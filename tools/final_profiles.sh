@@ -1,7 +1,7 @@
 R=$PWD
 mkdir -p gpurun_out/final
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -- python $R/bench.py --no-cpu-baseline > /tmp/log_kt 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -- python $R/bench.py --full --no-cpu-baseline > /tmp/log_kt 2>&1
 grep '^{"metric"' /tmp/log_kt > $R/gpurun_out/final/bench_under_kernel_trace.json
 db=$(find /tmp/prof_kt -name "*.db" | head -1)
 python $R/tools/prof_db.py $db 40 > $R/gpurun_out/final/kernel_trace.txt

@@ -22,7 +22,7 @@ def main(path, top=30):
 
 def last_n(path, kernel_substr, n):
     """Average duration of the LAST n dispatches of the kernels whose name contains kernel_substr
-    (bench.py's roofline loop is the tail of the run)."""
+    (the roofline loop of `bench.py --full` is the tail of the run)."""
     db = sqlite3.connect(path)
     cur = db.cursor()
     tabs = [r[0] for r in cur.execute("select name from sqlite_master where type='table'")]

@@ -26,7 +26,7 @@ def main(path, top=12):
 
 def last_n(path, kernel_substr, n):
     """Average of each counter over the LAST n dispatches of the kernels whose name contains
-    kernel_substr (bench.py's roofline loop is the tail of the run)."""
+    kernel_substr (the roofline loop of `bench.py --full` is the tail of the run)."""
     db = sqlite3.connect(path)
     cur = db.cursor()
     tabs = {t.split("_0000")[0]: t for (t,) in cur.execute("select name from sqlite_master where type='table'")}

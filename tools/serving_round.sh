@@ -4,7 +4,7 @@
 # arriving at once with max_num_seqs 256 (decode batches up to 256 rows).   usage: tools/serving_round.sh r03
 TAG=${1:-r03}
 R=$PWD
-O=$R/gpurun_out/$TAG
+O=${OUT_DIR:-$R/bench_out}/$TAG
 mkdir -p $O
 MODEL=$(python - <<PY
 import sys; sys.path.insert(0, "$R/tests")

@@ -13,4 +13,4 @@ for n in 32 256; do
   timeout 600 python3 $R/nano-vllm-ascend_amd/bench/throughput_bench.py --model $MODEL --max-num-seqs $n 2>/dev/null | grep '^{' > $O/throughput_max_num_seqs_$n.json
   python3 -c "import json;d=json.load(open('$O/throughput_max_num_seqs_$n.json'));print('max_num_seqs',$n,round(d['throughput_tok_s']),'tok/s',round(d['seconds'],2),'s')"
 done
-timeout 900 python3 bench.py --gpus 8 --steps 8 --warmup 2 --no-cpu-baseline > $O/bench_gpus8_dry_run.json 2> $O/bench_gpus8_dry_run.err; echo "dry run rc=$?"; tail -c 600 $O/bench_gpus8_dry_run.json
+timeout 900 python3 bench.py --gpus 8 --steps 8 --warmup 2 --full > $O/bench_gpus8_dry_run.json 2> $O/bench_gpus8_dry_run.err; echo "dry run rc=$?"; tail -c 600 $O/bench_gpus8_dry_run.json
