@@ -58,6 +58,7 @@ enum {
 #define MI_HEAD_DIM        128  /* head_dim of the fragment-native kernels (all Qwen3 sizes); 64: mi_*_plain */
 #define MI_KV_TILE_TOKENS  16
 #define MI_KV_TILE_ELEMS   2048
+#define MI_KV8_TILE_BYTES  2112  /* fp8 KV cache: 2048 e4m3 values + the 16 fp32 scales of the tile's tokens */
 
 /* ---- library info -------------------------------------------------------- */
 const char* mi_strerror(int code);
@@ -122,6 +123,47 @@ int mi_kv_cache_gather(const mi_bf16* cache, int is_v,
                        const int32_t* slot_flat, int n,
                        mi_bf16* out, int n_kv_heads, int head_dim, int block_size,
                        mi_stream stream);
+
+/* ---- opt-in fp8 (OCP e4m3) KV cache (no reference counterpart; csrc/paged_attn_fp8kv.hip) ----
+ * One layer's K (or V) cache is  [num_blocks][n_kv_heads][block_size/16][MI_KV8_TILE_BYTES] bytes; head_dim = 128.
+ * A tile holds 2048 e4m3 values, then the 16 fp32 scales of its tokens (token t at byte 2048 + 4 t).  Value (t, d)
+ * of a K tile sits at byte  (d/64)*1024 + (((d%32)/8)*16 + t)*16 + ((d%64)/32)*8 + d%8,
+ * of a V tile at            (d/64)*1024 + ((t/4)*16 + d%16)*16 + ((d%64)/16)*4 + t%4:
+ * a wavefront's 1 KiB load (16 B per lane) dequantises in registers into two MFMA 16x16x32 bf16 operand fragments.
+ * Quantisation rule, per (token, kv head) row x[128]: amax = max|x|; e = max(floor(log2 amax) - 7, -120), e = 0 for
+ * amax = 0; scale = 2^e; value = RNE_e4m3fn(x / scale).  x / scale and value * scale are exact, so attention over
+ * this cache is attention over the dequantised bf16 rows.  Caches must start zero-filled. */
+
+/* Quantise and scatter the step's K / V rows ([n_tokens, n_kv_heads, 128] bf16, row strides in elements).  slots:
+ * slot_is_2d = 0: [n_tokens] flat slots (prefill), 1: [n_tokens][2] = {block id, offset} (decode); a negative slot
+ * or block id skips the row. */
+int mi_kv_store_fp8(const mi_bf16* k, const mi_bf16* v, int64_t k_row_stride, int64_t v_row_stride,
+                    uint8_t* k_cache, uint8_t* v_cache, const int32_t* slots, int slot_is_2d, int n_tokens,
+                    int n_kv_heads, int head_dim, int block_size, mi_stream stream);
+
+/* mi_paged_attn_decode over an fp8 cache (same arguments, same workspace, same result contract: attention over the
+ * dequantised rows).  n_q_heads / n_kv_heads in {1, 2, 4, 8, 16}, head_dim 128.  The step's new row is read from
+ * the cache: mi_kv_store_fp8 runs in front of this launch. */
+int mi_paged_attn_decode_fp8kv(const mi_bf16* q, int64_t q_row_stride,
+                               const uint8_t* k_cache, const uint8_t* v_cache,
+                               const int32_t* block_table, int table_stride,
+                               const int32_t* context_lens,
+                               mi_bf16* out, void* workspace, size_t ws_bytes,
+                               int batch, int n_q_heads, int n_kv_heads, int head_dim,
+                               int block_size, float scale, mi_stream stream);
+
+/* Prefill: dequantise the blocks that block_table [n_seqs][table_stride] references for the first kv_lens[s] tokens
+ * of each sequence from one layer's fp8 cache into a one-layer bf16 scratch cache in the fragment-native layout above,
+ * at the SAME block ids - mi_paged_attn_prefill then runs over the scratch with the step's own block table. */
+int mi_kv_fp8_expand(const uint8_t* k_cache, const uint8_t* v_cache, mi_bf16* k_scratch, mi_bf16* v_scratch,
+                     const int32_t* block_table, int table_stride, const int32_t* kv_lens, int n_seqs,
+                     int n_kv_heads, int head_dim, int block_size, mi_stream stream);
+
+/* Test/debug helper: rows of an fp8 cache in logical layout - out_q [n, n_kv_heads*128] e4m3 bytes and out_scale
+ * [n, n_kv_heads] fp32, one row per flat slot (negative: zeros). */
+int mi_kv_cache_gather_fp8(const uint8_t* cache, int is_v, const int32_t* slot_flat, int n,
+                           uint8_t* out_q, float* out_scale, int n_kv_heads, int head_dim, int block_size,
+                           mi_stream stream);
 
 /* ---- paged attention ------------------------------------------------------ */
 /* Bytes of workspace mi_paged_attn_decode needs for (batch, n_q_heads). */

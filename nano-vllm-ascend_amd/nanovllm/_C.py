@@ -27,6 +27,7 @@ MI_EUNSUPPORTED = -2
 HEAD_DIM = 128
 KV_TILE_TOKENS = 16
 KV_TILE_ELEMS = 2048
+KV8_TILE_BYTES = 2112  # fp8 KV cache tile: 2048 e4m3 values + 16 fp32 scales
 
 
 class MiError(RuntimeError):
@@ -57,6 +58,13 @@ _SIGNATURES = {
     "mi_reshape_and_cache": (c_int, [_p, _p, c_int64, c_int64, _p, _p, _p, c_int, c_int, c_int, c_int, _p]),
     "mi_scatter_update_kv": (c_int, [_p, _p, c_int64, c_int64, _p, _p, _p, c_int, c_int, c_int, c_int, _p]),
     "mi_kv_cache_gather": (c_int, [_p, c_int, _p, c_int, _p, c_int, c_int, c_int, _p]),
+    "mi_kv_store_fp8": (c_int, [_p, _p, c_int64, c_int64, _p, _p, _p, c_int, c_int, c_int, c_int, c_int, _p]),
+    "mi_paged_attn_decode_fp8kv": (
+        c_int,
+        [_p, c_int64, _p, _p, _p, c_int, _p, _p, _p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, _p],
+    ),
+    "mi_kv_fp8_expand": (c_int, [_p, _p, _p, _p, _p, c_int, _p, c_int, c_int, c_int, c_int, _p]),
+    "mi_kv_cache_gather_fp8": (c_int, [_p, c_int, _p, c_int, _p, _p, c_int, c_int, c_int, _p]),
     "mi_paged_attn_decode_workspace": (c_size_t, [c_int, c_int]),
     "mi_paged_attn_decode": (
         c_int,

@@ -48,6 +48,7 @@ class Config:
     decode_lookahead: bool = True  # one GPU: queue decode step k+1 before step k's tokens reach the host
     sampling_seed: int | None = None  # seed of the temperature sampler; None: drawn from os.urandom per engine
     quantization: str | None = None  # "fp8": e4m3 weights + per-row scales for the decode GEMMs (no reference counterpart)
+    kv_cache_dtype: str = "bf16"  # "fp8": e4m3 KV cache, one power-of-two scale per (token, kv head) (no reference counterpart)
     prefix_aware_prefill: bool = True  # skip the tokens of cache-hit prefix blocks in prefill (False: recompute, as the reference)
     prefill_graphs: bool = True  # prefill steps of up to 4 sequences / 4096 tokens replay bucketed hipGraphs (engine/model_runner.py)
     gc_control: bool = True  # engine/host_gc.py: freeze after warm-up, no automatic collection inside step(), full passes only when idle
@@ -61,6 +62,7 @@ class Config:
         assert 1 <= self.tensor_parallel_size <= 8
         assert self.graph_mode in {m.value for m in GraphMode}, self.graph_mode
         assert self.quantization in (None, "fp8"), self.quantization
+        assert self.kv_cache_dtype in ("bf16", "fp8"), self.kv_cache_dtype
         if self.sampling_seed is None:
             self.sampling_seed = int.from_bytes(os.urandom(8), "little") >> 1
         if self.hf_config is None:
@@ -75,6 +77,26 @@ class Config:
         if eos is not None:
             self.eos = eos[0] if isinstance(eos, (list, tuple)) else eos
         assert self.max_num_batched_tokens >= self.max_model_len
+        self.check_kv_cache_dtype()
+
+    def check_kv_cache_dtype(self) -> None:
+        """What the fp8 KV cache kernels (csrc/paged_attn_fp8kv.hip) are built for; checked when the Config is made and
+        again by ModelRunner.__init__, i.e. before a worker process exists."""
+        if self.kv_cache_dtype != "fp8":
+            return
+        text = getattr(self.hf_config, "text_config", self.hf_config)
+        hq, hkv = text.num_attention_heads, text.num_key_value_heads
+        head_dim = getattr(text, "head_dim", None) or text.hidden_size // hq
+        if self.tensor_parallel_size > 1:
+            raise NotImplementedError('kv_cache_dtype="fp8" with tensor_parallel_size > 1: the fp8 cache path has only '
+                                      "been built and verified on one GPU")
+        if head_dim != 128:
+            raise NotImplementedError(f'kv_cache_dtype="fp8" with head_dim {head_dim}: the fp8 tile layout and its '
+                                      "kernels are written for 128-wide heads")
+        if hq % hkv or hq // hkv not in (1, 2, 4, 8, 16):
+            raise NotImplementedError(f'kv_cache_dtype="fp8" with {hq} query heads over {hkv} kv heads: the fp8 decode '
+                                      "attention takes GQA groups 1, 2, 4, 8, 16 (not groups of 7 or the plain-layout "
+                                      "geometries)")
 
     @property
     def use_graphs(self) -> bool:

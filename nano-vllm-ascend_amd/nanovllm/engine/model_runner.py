@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from nanovllm import ops
+from nanovllm._C import KV8_TILE_BYTES
 from nanovllm.config import Config
 from nanovllm.engine import batch_meta
 from nanovllm.engine.rpc import StepChannel
@@ -83,6 +84,7 @@ class ModelRunner:
         self.world_size = config.tensor_parallel_size
         self.rank = rank
         self.event = event
+        config.check_kv_cache_dtype()
 
         if not torch.cuda.is_available():
             raise RuntimeError("nanovllm (MI355X build) needs a HIP device: there is no CPU execution path")
@@ -366,6 +368,10 @@ class ModelRunner:
         head_dim = getattr(hf, "head_dim", None) or hf.hidden_size // hf.num_attention_heads
         layers = hf.num_hidden_layers
         block_bytes = 2 * layers * self.block_size * n_kv * head_dim * 2
+        fp8 = cfg.kv_cache_dtype == "fp8"
+        if fp8:  # e4m3 data + scales in every layer, and the block's share of the one-layer bf16 prefill scratch
+            block_bytes = (2 * layers * (self.block_size // 16) * n_kv * KV8_TILE_BYTES
+                           + 2 * self.block_size * n_kv * head_dim * 2)
         if cfg.num_kvcache_blocks <= 0:
             available = total * cfg.gpu_memory_utilization - used - peak + current
             cfg.num_kvcache_blocks = int(available) // block_bytes
@@ -385,6 +391,20 @@ class ModelRunner:
         from nanovllm import ops
 
         hq = hf.num_attention_heads // self.world_size
+        if fp8:
+            self.kv_cache = torch.zeros((2, layers, *ops.kv_cache_shape_fp8(alloc_blocks, n_kv, self.block_size)),
+                                        dtype=torch.uint8, device=self.device)
+            self.kv_scratch = torch.zeros((2, *ops.kv_cache_shape(alloc_blocks, n_kv, self.block_size, head_dim)),
+                                          dtype=torch.bfloat16, device=self.device)
+            scratch = (self.kv_scratch[0, : cfg.num_kvcache_blocks], self.kv_scratch[1, : cfg.num_kvcache_blocks])
+            layer_id = 0
+            for module in self.model.modules():
+                if hasattr(module, "k_cache") and hasattr(module, "v_cache"):
+                    module.set_fp8_cache(self.kv_cache[0, layer_id, : cfg.num_kvcache_blocks],
+                                         self.kv_cache[1, layer_id, : cfg.num_kvcache_blocks], scratch)
+                    layer_id += 1
+            assert layer_id == layers
+            return
         if ops.attention_is_plain(hq, n_kv, head_dim):  # head_dim 64 / odd GQA groups: [blocks, kv heads, block, head_dim]
             shape = ops.kv_cache_shape_plain(alloc_blocks, n_kv, self.block_size, head_dim)
         else:

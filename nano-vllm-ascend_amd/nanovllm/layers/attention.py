@@ -7,6 +7,9 @@ Same constructor and forward signature as the reference class; the runner inject
 The caches use the fragment-native layout of include/mi355_nanovllm.h (head_dim 128 or 64; 1, 2, 4, 7, 8 or 16 query
 heads per kv head) - or, for the head geometries those kernels are not built for (`self.plain`), the plain
 [blocks, kv heads, block, head_dim] layout and the mi_*_plain kernels (csrc/attn_plain.hip).
+With `Config.kv_cache_dtype == "fp8"` the runner injects uint8 caches in the e4m3 tile layout plus a one-layer bf16
+scratch (`kv_scratch`): rows are quantised on store, decode attends the fp8 cache directly, prefill attends the scratch
+after mi_kv_fp8_expand has dequantised the step's blocks into it (csrc/paged_attn_fp8kv.hip).
 """
 from __future__ import annotations
 
@@ -31,10 +34,19 @@ class Attention(nn.Module):
         # the fused launches (models/qwen3.py) are written for 128-wide heads and power-of-two groups; head_dim 64 and
         # groups of 7 take the module-by-module sequence RoPE -> store -> attention on the same fragment-native kernels
         self.fusable = ops.attention_is_fusable(num_heads, num_kv_heads, head_dim)
+        self.kv_scratch = None  # fp8 cache only: (k, v) bf16 scratch of one layer, shared by all layers
+
+    def set_fp8_cache(self, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_scratch) -> None:
+        """fp8 KV cache: the store is a launch of its own (the fused step prologues write bf16 rows), so the model
+        takes the operator-by-operator sequence norm -> RoPE -> store -> attention."""
+        self.k_cache, self.v_cache, self.kv_scratch = k_cache, v_cache, kv_scratch
+        self.fusable = False
 
     def _store_kvcache(self, k: torch.Tensor, v: torch.Tensor, context) -> None:
         """attention.py:22-35: flat slots in prefill, [block, offset] pairs in decode."""
-        if self.plain:
+        if self.kv_scratch is not None:
+            ops.kv_store_fp8(k, v, self.k_cache, self.v_cache, context.slot_mapping, self.num_kv_heads, self.block_size)
+        elif self.plain:
             ops.kv_store_plain(k, v, self.k_cache, self.v_cache, context.slot_mapping, self.num_kv_heads, self.block_size)
         elif context.slot_mapping.dim() == 2:
             ops.scatter_update_kv(k, v, self.k_cache, self.v_cache, context.slot_mapping, self.num_kv_heads,
@@ -55,6 +67,13 @@ class Attention(nn.Module):
             kv_lens = context.kv_lens
             if kv_lens is None:
                 kv_lens = (context.cu_seqlens_k[1:] - context.cu_seqlens_k[:-1]).contiguous()
+            if self.kv_scratch is not None:  # attend exactly the values decode will read: the dequantised cache
+                ks, vs = self.kv_scratch
+                ops.kv_fp8_expand(self.k_cache, self.v_cache, ks, vs, context.block_tables, kv_lens, self.num_kv_heads,
+                                  self.block_size)
+                return ops.paged_attn_prefill(q, ks, vs, context.block_tables, context.cu_seqlens_q, kv_lens,
+                                              context.max_seqlen_q, self.num_heads, self.num_kv_heads, self.block_size,
+                                              self.scale)
             if self.plain:
                 return ops.paged_attn_prefill_plain(q, self.k_cache, self.v_cache, context.block_tables,
                                                     context.cu_seqlens_q, kv_lens, context.max_seqlen_q, self.num_heads,
@@ -62,6 +81,9 @@ class Attention(nn.Module):
             return ops.paged_attn_prefill(q, self.k_cache, self.v_cache, context.block_tables,
                                           context.cu_seqlens_q, kv_lens, context.max_seqlen_q, self.num_heads,
                                           self.num_kv_heads, self.block_size, self.scale)
+        if self.kv_scratch is not None:
+            return ops.paged_attn_decode_fp8kv(q, self.k_cache, self.v_cache, context.block_tables, context.context_lens,
+                                               self.num_heads, self.num_kv_heads, self.block_size, self.scale)
         if self.plain:
             return ops.paged_attn_decode_plain(q, self.k_cache, self.v_cache, context.block_tables, context.context_lens,
                                                self.num_heads, self.num_kv_heads, self.block_size, self.scale)

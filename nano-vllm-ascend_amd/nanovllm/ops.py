@@ -70,6 +70,96 @@ def kv_cache_gather(cache, is_v: bool, slot_flat, n_kv_heads: int, block_size: i
     return out
 
 
+# --------------------------------------------------------------------------- fp8 (e4m3) KV cache
+def kv_cache_shape_fp8(num_blocks: int, n_kv_heads: int, block_size: int) -> tuple[int, int, int, int]:
+    """Shape (uint8) of one layer's K (or V) fp8 cache: a tile of 2048 e4m3 values + 16 fp32 scales per (16 slots,
+    kv head).  Allocate it zero-filled."""
+    assert block_size % _C.KV_TILE_TOKENS == 0
+    return (num_blocks, n_kv_heads, block_size // _C.KV_TILE_TOKENS, _C.KV8_TILE_BYTES)
+
+
+def _fp8_cache(*caches: torch.Tensor) -> None:
+    for c in caches:
+        if c.dtype != torch.uint8 or c.shape[-1] != _C.KV8_TILE_BYTES:
+            raise _C.MiError(f"expected a uint8 fp8 KV cache [..., {_C.KV8_TILE_BYTES}], got {c.dtype} {tuple(c.shape)}")
+
+
+def kv_store_fp8(k, v, k_cache, v_cache, slots, n_kv_heads: int, block_size: int) -> None:
+    """Quantise (one power-of-two scale per token and kv head) and scatter the step's K / V rows; `slots` is [n] flat
+    or [n, 2] = {block, offset}."""
+    require_gpu(k, v, k_cache, v_cache, slots)
+    _bf16(k, v)
+    _fp8_cache(k_cache, v_cache)
+    n = k.shape[0]
+    assert k.stride(-1) == 1 and v.stride(-1) == 1 and k.shape[-1] == HEAD_DIM
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape in ((n,), (n, 2))
+    check(
+        lib.mi_kv_store_fp8(ptr(k), ptr(v), k.stride(0), v.stride(0), ptr(k_cache), ptr(v_cache), ptr(slots),
+                            int(slots.dim() == 2), n, n_kv_heads, HEAD_DIM, block_size, stream()),
+        "mi_kv_store_fp8",
+    )
+
+
+def kv_cache_gather_fp8(cache, is_v: bool, slot_flat, n_kv_heads: int, block_size: int):
+    """Rows of an fp8 cache in logical layout: (e4m3 bytes [n, n_kv_heads*128] uint8, scales [n, n_kv_heads] fp32)."""
+    require_gpu(cache, slot_flat)
+    _fp8_cache(cache)
+    n = slot_flat.numel()
+    out_q = torch.empty((n, n_kv_heads * HEAD_DIM), dtype=torch.uint8, device=cache.device)
+    out_s = torch.empty((n, n_kv_heads), dtype=torch.float32, device=cache.device)
+    check(
+        lib.mi_kv_cache_gather_fp8(ptr(cache), int(is_v), ptr(slot_flat), n, ptr(out_q), ptr(out_s), n_kv_heads,
+                                   HEAD_DIM, block_size, stream()),
+        "mi_kv_cache_gather_fp8",
+    )
+    return out_q, out_s
+
+
+def kv_fp8_expand(k_cache, v_cache, k_scratch, v_scratch, block_tables, kv_lens, n_kv_heads: int, block_size: int) -> None:
+    """Dequantise the blocks the step's tables reference into the one-layer bf16 scratch cache (same block ids)."""
+    require_gpu(k_cache, v_cache, k_scratch, v_scratch, block_tables, kv_lens)
+    _fp8_cache(k_cache, v_cache)
+    _bf16(k_scratch, v_scratch)
+    assert k_scratch.shape[0] >= k_cache.shape[0] and v_scratch.shape[0] >= v_cache.shape[0]
+    assert block_tables.dtype == torch.int32 and block_tables.stride(1) == 1
+    assert kv_lens.dtype == torch.int32 and kv_lens.is_contiguous()
+    check(
+        lib.mi_kv_fp8_expand(ptr(k_cache), ptr(v_cache), ptr(k_scratch), ptr(v_scratch), ptr(block_tables),
+                             block_tables.stride(0), ptr(kv_lens), kv_lens.numel(), n_kv_heads, HEAD_DIM, block_size,
+                             stream()),
+        "mi_kv_fp8_expand",
+    )
+
+
+def paged_attn_decode_fp8kv(q, k_cache, v_cache, block_tables, context_lens, n_q_heads: int, n_kv_heads: int,
+                            block_size: int, scale: float, out=None, workspace=None) -> torch.Tensor:
+    require_gpu(q, k_cache, v_cache, block_tables, context_lens)
+    _bf16(q)
+    _fp8_cache(k_cache, v_cache)
+    batch = q.shape[0]
+    q2 = q.view(batch, -1) if q.dim() == 3 else q
+    assert q2.stride(1) == 1 and q2.shape[1] == n_q_heads * HEAD_DIM
+    assert block_tables.dtype == torch.int32 and block_tables.stride(1) == 1
+    assert context_lens.dtype == torch.int32 and context_lens.is_contiguous()
+    if out is None:
+        out = torch.empty((batch, n_q_heads * HEAD_DIM), dtype=_BF16, device=q.device)
+    if workspace is None:
+        workspace = attn_workspace(q.device, batch, n_q_heads)
+    check(
+        lib.mi_paged_attn_decode_fp8kv(ptr(q2), q2.stride(0), ptr(k_cache), ptr(v_cache), ptr(block_tables),
+                                       block_tables.stride(0), ptr(context_lens), ptr(out), ptr(workspace),
+                                       workspace.numel() * workspace.element_size(), batch, n_q_heads, n_kv_heads,
+                                       HEAD_DIM, block_size, float(scale), stream()),
+        "mi_paged_attn_decode_fp8kv",
+    )
+    return out
+
+
+def kv_fp8_supported(n_q_heads: int, n_kv_heads: int, head_dim: int) -> bool:
+    """The head geometries the fp8-KV kernels are built for: head_dim 128, GQA groups 1, 2, 4, 8, 16."""
+    return head_dim == HEAD_DIM and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8, 16)
+
+
 # --------------------------------------------------------------------------- attention
 _WORKSPACES: dict[torch.device, torch.Tensor] = {}
 

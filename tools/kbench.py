@@ -146,6 +146,55 @@ def plain_attention():
                   flush=True)
 
 
+def fp8_kv_attention():
+    """The fp8-KV decode attention launch beside the bf16 one: bs 32, 8 kv heads x 2, ctx 1049 (the middle of the timed
+    bench window), distinct caches per layer, interleaved rounds; and the launches the fp8 path runs in front of it
+    (q-norm, k-norm, RoPE, quantising store) where the bf16 path has its fused step prologue."""
+    B, c, bs, hq, hkv, L = 32, int(os.environ.get("CTX", 1049)), 16, 16, 8, 28
+    nb = (c + bs - 1) // bs
+    nblk = B * nb
+    g = torch.Generator(device="cpu").manual_seed(0)
+    kc = [torch.randn(ops.kv_cache_shape(nblk, hkv, bs), device=DEV).bfloat16() for _ in range(L)]
+    vc = [torch.randn(ops.kv_cache_shape(nblk, hkv, bs), device=DEV).bfloat16() for _ in range(L)]
+    # finite e4m3 bytes everywhere (0x7f / 0xff are NaN) and scale 1: timing needs no meaningful values
+    k8 = [torch.randint(0, 0x70, ops.kv_cache_shape_fp8(nblk, hkv, bs), dtype=torch.uint8, device=DEV) for _ in range(L)]
+    v8 = [torch.randint(0, 0x70, ops.kv_cache_shape_fp8(nblk, hkv, bs), dtype=torch.uint8, device=DEV) for _ in range(L)]
+    for t8 in k8 + v8:
+        t8[..., 2048:].view(torch.float32).fill_(1.0)
+    perm = torch.randperm(nblk, generator=g).to(torch.int32).view(B, nb).to(DEV)
+    ctxl = torch.full((B,), c, dtype=torch.int32, device=DEV)
+    q = torch.randn(B, hq * 128, device=DEV).bfloat16()
+    out = torch.empty(B, hq * 128, dtype=torch.bfloat16, device=DEV)
+    ws = ops.attn_workspace(DEV, B, hq)
+    qkv = torch.randn(B, (hq + 2 * hkv) * 128, device=DEV).bfloat16()
+    q_, k_, v_ = (t.view(B, -1, 128) for t in qkv.split([hq * 128, hkv * 128, hkv * 128], dim=-1))
+    w128 = torch.ones(128, device=DEV).bfloat16()
+    rope_t = torch.randn(4096, 128, device=DEV)
+    pos = torch.full((B,), c - 1, dtype=torch.int64, device=DEV)
+    sl = torch.stack([perm[:, (c - 1) // bs], torch.full((B,), (c - 1) % bs, dtype=torch.int32, device=DEV)], 1).contiguous()
+    byt16 = B * 2 * c * hkv * 128 * 2
+    byt8 = B * 2 * c * hkv * (128 + 4)
+
+    def front(l):
+        qr, kr = ops.rope(pos, ops.rmsnorm(q_, w128, 1e-6), ops.rmsnorm(k_, w128, 1e-6), rope_t, hq, hkv)
+        ops.kv_store_fp8(kr, v_, k8[l], v8[l], sl, hkv, bs)
+        return qr
+
+    for rnd in range(3):
+        t = timeit(lambda l: ops.paged_attn_decode(q, kc[l], vc[l], perm, ctxl, hq, hkv, bs, 128 ** -0.5, out=out, workspace=ws), L)
+        print(f"#{rnd} paged_attn_decode        bf16 KV ctx={c}: {t * 1e6:7.2f} us  {byt16 / 1e6:6.1f} MB  {byt16 / t / PEAK:5.3f} of 8 TB/s")
+        t = timeit(lambda l: ops.paged_attn_decode_fp8kv(q, k8[l], v8[l], perm, ctxl, hq, hkv, bs, 128 ** -0.5, out=out, workspace=ws), L)
+        print(f"#{rnd} paged_attn_decode_fp8kv  fp8 KV  ctx={c}: {t * 1e6:7.2f} us  {byt8 / 1e6:6.1f} MB  {byt8 / t / PEAK:5.3f} of 8 TB/s")
+        t = timeit(lambda l: ops.paged_attn_decode_fused(qkv, w128, w128, 1e-6, pos, rope_t, sl, kc[l], vc[l], perm, ctxl, hq, hkv,
+                                                         bs, 128 ** -0.5, out=out, workspace=ws), L)
+        print(f"#{rnd} bf16 fused step (norm + RoPE + store + attention, one launch): {t * 1e6:7.2f} us")
+        t = timeit(front, L)
+        print(f"#{rnd} fp8 front launches (q-norm, k-norm, RoPE, quantising store):   {t * 1e6:7.2f} us")
+        t = timeit(lambda l: ops.paged_attn_decode_fp8kv(front(l), k8[l], v8[l], perm, ctxl, hq, hkv, bs, 128 ** -0.5, out=out,
+                                                         workspace=ws), L)
+        print(f"#{rnd} fp8 step (front launches + attention, five launches):          {t * 1e6:7.2f} us")
+
+
 def head_and_sampler():
     """The head GEMM (151936 x 1024, 32 rows) alone, with the pick epilogue, and the standalone sampler."""
     M, N, K = 32, 151936, 1024
@@ -308,6 +357,8 @@ def main():
         return prefill_attention_order()
     if os.environ.get("KBENCH_ONLY") == "prefill":
         return prefill_attention()
+    if os.environ.get("KBENCH_ONLY") == "fp8kv":
+        return fp8_kv_attention()
     if os.environ.get("KBENCH_ONLY") == "head":
         return head_and_sampler()
     B, ctx, bs, hq, hkv, L = 32, int(os.environ.get("CTX", 1024)), 16, 16, 8, 28
