@@ -152,6 +152,24 @@ int mi_paged_attn_decode_fp8kv(const mi_bf16* q, int64_t q_row_stride,
                                int batch, int n_q_heads, int n_kv_heads, int head_dim,
                                int block_size, float scale, mi_stream stream);
 
+/* mi_paged_attn_decode_fused over an fp8 cache (same arguments with uint8_t caches, same return codes, same split
+ * rule): q_norm / k_norm / RoPE (qwen3.py:83-88), the quantising store of the new token's K / V row
+ * (attention.py:32-35) and the attention (attention.py:63-93) in one launch, straight from the packed qkv rows.
+ * Output and every cache byte are bit-identical to mi_rmsnorm (q, k) + mi_rope + mi_kv_store_fp8 followed by
+ * mi_paged_attn_decode_fp8kv.  Rows with context_len <= 0 produce zeros and write nothing; a slot with a negative
+ * block id or offset is attended but not stored.  q_w / k_w: both given or both NULL.  n_q_heads / n_kv_heads in
+ * {1, 2, 4, 8, 16}, head_dim 128. */
+int mi_paged_attn_decode_fp8kv_fused(const mi_bf16* qkv, int64_t qkv_row_stride,
+                                     const mi_bf16* q_w, const mi_bf16* k_w, float eps,
+                                     const int64_t* positions, const float* cos_sin,
+                                     const int32_t* slot_2d,
+                                     uint8_t* k_cache, uint8_t* v_cache,
+                                     const int32_t* block_table, int table_stride,
+                                     const int32_t* context_lens,
+                                     mi_bf16* out, void* workspace, size_t ws_bytes,
+                                     int batch, int n_q_heads, int n_kv_heads, int head_dim,
+                                     int block_size, float scale, mi_stream stream);
+
 /* Prefill: dequantise the blocks that block_table [n_seqs][table_stride] references for the first kv_lens[s] tokens
  * of each sequence from one layer's fp8 cache into a one-layer bf16 scratch cache in the fragment-native layout above,
  * at the SAME block ids - mi_paged_attn_prefill then runs over the scratch with the step's own block table. */

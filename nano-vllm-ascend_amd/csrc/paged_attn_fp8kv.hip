@@ -32,6 +32,7 @@
 #include "mi_common.hpp"
 #include "kv_store.hpp"
 #include "prefill_common.hpp"
+#include "step_prologue.hpp"
 
 namespace mi {
 
@@ -61,6 +62,17 @@ __device__ __forceinline__ bf16x8 dq8(uint32_t w0, uint32_t w1) {
   return as_frag(u32x4{a[0], a[1], b[0], b[1]});
 }
 
+// The quantisation rule, shared by the store kernel and the fused decode step.  floor(log2 amax) is the exponent field
+// (a bf16 subnormal maximum falls under the clamp in any case).
+__device__ __forceinline__ int kv8_exponent(float amax) {
+  return amax == 0.f ? 0 : max((int)(__float_as_uint(amax) >> 23) - 127 - 7, -120);
+}
+// four values times 2^-e -> four e4m3 bytes, the first in the low byte
+__device__ __forceinline__ uint32_t quant4(float a, float b, float c, float d, float inv) {
+  const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a * inv, b * inv, 0, false);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c * inv, d * inv, w, true);
+}
+
 // ---------------------------------------------------------------------------
 // store: 8 lanes per (token, kv head, K | V) row, 16 values each (dims 8 j .. and 64 + 8 j ..)
 // ---------------------------------------------------------------------------
@@ -84,16 +96,13 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(const uint16_t* __res
   amax = xor_max<1>(amax);
   amax = xor_max<2>(amax);
   amax = xor_max<4>(amax);
-  // floor(log2 amax) is the exponent field (a bf16 subnormal maximum falls under the clamp in any case)
-  const int e = amax == 0.f ? 0 : max((int)(__float_as_uint(amax) >> 23) - 127 - 7, -120);
+  const int e = kv8_exponent(amax);
   const float inv = __uint_as_float((uint32_t)(127 - e) << 23), scale = __uint_as_float((uint32_t)(127 + e) << 23);
   uint32_t qa[2], qb[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a[4 * i] * inv, a[4 * i + 1] * inv, 0, false);
-    qa[i] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a[4 * i + 2] * inv, a[4 * i + 3] * inv, w, true);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(b[4 * i] * inv, b[4 * i + 1] * inv, 0, false);
-    qb[i] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(b[4 * i + 2] * inv, b[4 * i + 3] * inv, w, true);
+    qa[i] = quant4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3], inv);
+    qb[i] = quant4(b[4 * i], b[4 * i + 1], b[4 * i + 2], b[4 * i + 3], inv);
   }
   int64_t blk;
   int off;
@@ -283,17 +292,128 @@ __device__ __forceinline__ void attend_chunk8(const Chunk8& c, const bf16x8 (&Q)
   }
 }
 
+// ---- the fused step (FUSE): q/k-norm + RoPE + the quantising store of the step's token inside the attention launch ----
+// The new row as the prologue wave publishes it in LDS: K's 128 e4m3 bytes in TILE order (the 16 bytes of lane
+// (g, n = token) of fp8 load i at 64 i + 16 g), V's 128 bytes in dim order, then the two scales.
+struct NewRow8 {
+  __attribute__((aligned(16))) uint8_t k[128];
+  __attribute__((aligned(16))) uint8_t v[128];
+  float k_scale, v_scale;
+};
+
+// Second half of the prologue (the first, step_prologue_issue, ran ahead of the wave's tile loads; all 64 lanes are
+// here).  Query heads -> sm_q as bf16.  The k head (pass G / 16, lanes n == G % 16): lane g holds dims 8 g + 32 kk + e of
+// the normed, rotated, bf16-rounded row, so the row maximum is a lane-local maximum and two steps over g, and the
+// eight bytes of x[kk] are bytes 8 (kk % 2) .. of the lane's 16 bytes of fp8 load kk / 2 - the row is quantised where
+// it stands.  The V row (two dims per lane) takes a wave-wide maximum.  Both go to `row` for the wave that attends the
+// new token's tile and (k_tile / v_tile non-null: split 0, a real slot) into the cache.
 template <int G>
+__device__ __forceinline__ void step_prologue_finish8(const StepOperands<G>& o, bool has_norm, float eps, int lane,
+                                                      uint8_t* k_tile, uint8_t* v_tile, int tok, uint16_t* sm_q,
+                                                      NewRow8& row) {
+  const int g = lane >> 4, n = lane & 15;
+  u32x4 kq[2] = {};
+  float k_scale = 1.f;
+#pragma unroll
+  for (int ps = 0; ps < StepOperands<G>::PASSES; ++ps) {
+    const int hh = n + 16 * ps;
+    float x[4][8];
+    step_prologue_head<G>(o, ps, has_norm, eps, x);
+    if (hh < G) {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) *reinterpret_cast<u32x4*>(sm_q + hh * 128 + 8 * g + 32 * kk) = pack16(x[kk]);
+    }
+    if (ps == G / 16) {  // every lane quantises the head it holds (no divergence around the cross-lane maximum)
+      float amax = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(x[kk][i]));
+      amax = xor_max<16>(amax);
+      amax = xor_max<32>(amax);
+      const int e = kv8_exponent(amax);
+      const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
+      k_scale = __uint_as_float((uint32_t)(127 + e) << 23);
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        kq[kk >> 1][2 * (kk & 1)] = quant4(x[kk][0], x[kk][1], x[kk][2], x[kk][3], inv);
+        kq[kk >> 1][2 * (kk & 1) + 1] = quant4(x[kk][4], x[kk][5], x[kk][6], x[kk][7], inv);
+      }
+    }
+  }
+  const float v0 = lo_bf(o.v), v1 = hi_bf(o.v);
+  const int ev = kv8_exponent(wave_max(fmaxf(fabsf(v0), fabsf(v1))));
+  const float inv_v = __uint_as_float((uint32_t)(127 - ev) << 23), v_scale = __uint_as_float((uint32_t)(127 + ev) << 23);
+  const uint32_t vq = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v0 * inv_v, v1 * inv_v, 0, false) & 0xffffu;
+  const bool k_lane = n == G % 16;
+  if (k_lane) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *reinterpret_cast<u32x4*>(row.k + 64 * i + 16 * g) = kq[i];
+    if (g == 0) row.k_scale = k_scale;
+  }
+  *reinterpret_cast<uint16_t*>(row.v + 2 * lane) = (uint16_t)vq;
+  if (lane == 0) row.v_scale = v_scale;
+  // the cache stores come LAST: loads and stores retire on the same counter, a store in front of a wait would make it
+  // wait for the wave's tile loads as well
+  if (k_tile != nullptr && k_lane) {  // k8_tile_off(tok, 64 i + 8 g (+ 32)) = i * 1024 + (g * 16 + tok) * 16 (+ 8)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *reinterpret_cast<u32x4*>(k_tile + i * 1024 + (g * 16 + tok) * 16) = kq[i];
+    if (g == 0) *reinterpret_cast<float*>(k_tile + KV8_DATA + 4 * tok) = k_scale;
+  }
+  if (v_tile != nullptr) {
+    v_tile[v8_tile_off(tok, 2 * lane)] = (uint8_t)vq;
+    v_tile[v8_tile_off(tok, 2 * lane + 1)] = (uint8_t)(vq >> 8);
+    if (lane == 0) *reinterpret_cast<float*>(v_tile + KV8_DATA + 4 * tok) = v_scale;
+  }
+}
+
+// Overwrite token `tok` of tile TL of a loaded chunk with the step's row: the wave that attends the context's last
+// tile does not wait for the prologue wave's cache store (a load racing that store sees old or new bytes in exactly
+// the places rewritten here).  Of lane (g, n):
+//   K load i: the whole quad is token n            -> replaced where n == tok;
+//   V load i: dword w = tokens 4 g .. 4 g + 3 of dim 64 i + 16 w + n -> byte tok % 4 where g == tok / 4;
+//   scales:   component tok % 4 where g == tok / 4.
+// `hit` is wave-uniform; callers patch BOTH tiles of a chunk, each with its own `hit`, through branch-free masks over
+// static register indices (paged_attn.hip's patch_new_token says what the alternatives cost).
+template <int TL>
+__device__ __forceinline__ void patch_new_token8(Chunk8& c, const NewRow8& row, int tok, int g, int n, bool hit) {
+  const uint32_t m_k1 = hit && n == tok ? 0xffffffffu : 0u;
+  const bool mine = hit && g == (tok >> 2);
+  const uint32_t sh = (tok & 3) * 8, m_v1 = mine ? 0xffu << sh : 0u;
+  const u32x4 m_k = {m_k1, m_k1, m_k1, m_k1}, m_v = {m_v1, m_v1, m_v1, m_v1};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const u32x4 kn = *reinterpret_cast<const u32x4*>(row.k + 64 * i + 16 * g);
+    u32x4 vn;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) vn[w] = (uint32_t)row.v[64 * i + 16 * w + n] << sh;
+    c.k[TL][i] = (c.k[TL][i] & ~m_k) | (kn & m_k);
+    c.v[TL][i] = (c.v[TL][i] & ~m_v) | (vn & m_v);
+  }
+  const float ksn = row.k_scale, vsn = row.v_scale;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const bool sel = mine && (tok & 3) == r;
+    c.ks[TL][r] = sel ? ksn : c.ks[TL][r];
+    c.vs[TL][r] = sel ? vsn : c.vs[TL][r];
+  }
+}
+
+// FUSE = false: q is the [batch][n_q_heads * 128] matrix of prepared query heads and the caches are only read.
+// FUSE = true (mi_paged_attn_decode_fp8kv_fused): q is the packed qkv matrix, fs the prologue's operands; the last
+// wave of the workgroup (never a long run, see deal()) runs the prologue, split 0 writes the new row into the caches.
+template <int G, bool FUSE>
 __global__ __launch_bounds__(512) void paged_attn_decode_fp8kv_kernel(
-    const uint16_t* __restrict__ q, int64_t q_stride, const uint8_t* __restrict__ kc, const uint8_t* __restrict__ vc,
+    const uint16_t* __restrict__ q, int64_t q_stride, const uint8_t* kc, const uint8_t* vc,
     const int32_t* __restrict__ block_table, int table_stride, const int32_t* __restrict__ ctx_lens,
     float* __restrict__ part_o, float* __restrict__ part_ml, uint16_t* __restrict__ out, int n_q_heads, int tpb,
-    int tpb_shift, float scale_log2e) {
+    int tpb_shift, float scale_log2e, FusedStep fs) {
   constexpr int WAVES = 8, D = 128;
   __shared__ __attribute__((aligned(16))) float sm_o[WAVES][G][D];
   __shared__ float sm_m[WAVES][16];
   __shared__ float sm_l[WAVES][16];
   __shared__ __attribute__((aligned(16))) uint16_t sm_q[G][D];
+  __shared__ NewRow8 sm_new;  // FUSE: the step's K / V row, quantised
 
   const int split = blockIdx.x, splits = gridDim.x, h = blockIdx.y, b = blockIdx.z, n_kv_heads = gridDim.y;
   const int ctx = max(ctx_lens[b], 0);
@@ -324,7 +444,26 @@ __global__ __launch_bounds__(512) void paged_attn_decode_fp8kv_kernel(
   const int vw = split * WAVES + wave;
   const int t0 = 2 * deal(vw), t1 = min(n_tiles, 2 * deal(vw + 1));
 
-  if (wave == 0) {  // stage the G query heads (contiguous G * 256 bytes of the q row)
+  // FUSE: the token of this step sits at position ctx - 1, row new_tok of tile new_tile.  The prologue wave's
+  // operands (and the slot) are requested here, ahead of its tile loads.
+  const int new_tile = (ctx - 1) >> 4, new_tok = (ctx - 1) & 15;
+  const bool is_pro = FUSE && wave == WAVES - 1;
+  StepOperands<G> pro;
+  int32_t blk = 0, off = 0;
+  if (is_pro) {
+    blk = fs.slots[2 * b];
+    off = fs.slots[2 * b + 1];
+    step_prologue_issue<G>(pro, q + (int64_t)b * q_stride, n_q_heads, n_kv_heads, h, fs,
+                           fs.cos_sin + fs.positions[b] * 128, lane);
+  }
+  auto finish_prologue = [&]() __attribute__((always_inline)) {
+    const bool store = split == 0 && blk >= 0 && off >= 0;  // split 0 always has work (the longer runs come first)
+    const int64_t tile_w = kv8_tile_base(blk, h, off, n_kv_heads, tpb);
+    step_prologue_finish8<G>(pro, fs.q_w != nullptr, fs.eps, lane, store ? const_cast<uint8_t*>(kc) + tile_w : nullptr,
+                             store ? const_cast<uint8_t*>(vc) + tile_w : nullptr, off & 15, &sm_q[0][0], sm_new);
+  };
+
+  if (!FUSE && wave == 0) {  // stage the G query heads (contiguous G * 256 bytes of the q row)
     for (int c = lane; c < G * (D / 8); c += 64)
       *reinterpret_cast<u32x4*>(&sm_q[0][0] + 8 * c) =
           *reinterpret_cast<const u32x4*>(q + (int64_t)b * q_stride + (int64_t)h * G * D + 8 * c);
@@ -353,8 +492,24 @@ __global__ __launch_bounds__(512) void paged_attn_decode_fp8kv_kernel(
   int ta = t0, tb = t0 + 2;
   auto load_a = [&]() __attribute__((always_inline)) { load_chunk8(kc_h, vc_h, tile_off(ta), tile_off(second(ta)), lane, A); };
   auto load_b = [&]() __attribute__((always_inline)) { load_chunk8(kc_h, vc_h, tile_off(tb), tile_off(second(tb)), lane, B); };
-  auto attend_a = [&]() __attribute__((always_inline)) { attend_chunk8(A, Q, ta * 16, limit_of(ta), scale_log2e, g, m, l, acc); };
-  auto attend_b = [&]() __attribute__((always_inline)) { attend_chunk8(B, Q, tb * 16, limit_of(tb), scale_log2e, g, m, l, acc); };
+  auto attend_a = [&]() __attribute__((always_inline)) {
+    if constexpr (FUSE) {
+      if (ta == new_tile || ta + 1 == new_tile) {  // wave-uniform, true once per (sequence, kv head)
+        patch_new_token8<0>(A, sm_new, new_tok, g, n, ta == new_tile);
+        patch_new_token8<1>(A, sm_new, new_tok, g, n, ta + 1 == new_tile);
+      }
+    }
+    attend_chunk8(A, Q, ta * 16, limit_of(ta), scale_log2e, g, m, l, acc);
+  };
+  auto attend_b = [&]() __attribute__((always_inline)) {
+    if constexpr (FUSE) {
+      if (tb == new_tile || tb + 1 == new_tile) {
+        patch_new_token8<0>(B, sm_new, new_tok, g, n, tb == new_tile);
+        patch_new_token8<1>(B, sm_new, new_tok, g, n, tb + 1 == new_tile);
+      }
+    }
+    attend_chunk8(B, Q, tb * 16, limit_of(tb), scale_log2e, g, m, l, acc);
+  };
   auto load_q = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -365,8 +520,9 @@ __global__ __launch_bounds__(512) void paged_attn_decode_fp8kv_kernel(
   };
   if (tb < t1) {  // at least two chunks
     load_a();
+    if (is_pro) finish_prologue();  // under the latency of buffer A
     load_b();
-    __syncthreads();  // sm_q complete; this wave's tile loads are in flight behind the barrier
+    __syncthreads();  // sm_q (FUSE: and the new row) complete; this wave's tile loads are in flight behind the barrier
     load_q();
     while (tb + 4 < t1) {  // both buffers have a successor
       attend_a();
@@ -387,10 +543,12 @@ __global__ __launch_bounds__(512) void paged_attn_decode_fp8kv_kernel(
     }
   } else if (ta < t1) {  // a single chunk
     load_a();
+    if (is_pro) finish_prologue();
     __syncthreads();
     load_q();
     attend_a();
   } else {
+    if (is_pro) finish_prologue();
     __syncthreads();
   }
   l += __shfl_xor(l, 16, 64);
@@ -519,11 +677,11 @@ extern "C" int mi_kv_fp8_expand(const uint8_t* k_cache, const uint8_t* v_cache, 
   return check_launch();
 }
 
-extern "C" int mi_paged_attn_decode_fp8kv(const mi_bf16* q, int64_t q_row_stride, const uint8_t* k_cache,
-                                          const uint8_t* v_cache, const int32_t* block_table, int table_stride,
-                                          const int32_t* context_lens, mi_bf16* out, void* workspace, size_t ws_bytes,
-                                          int batch, int n_q_heads, int n_kv_heads, int head_dim, int block_size,
-                                          float scale, mi_stream stream) {
+// both decode entry points: fused == nullptr attends prepared query heads, otherwise q is the packed qkv matrix
+static int decode8_impl(const mi_bf16* q, int64_t q_row_stride, const uint8_t* k_cache, const uint8_t* v_cache,
+                        const int32_t* block_table, int table_stride, const int32_t* context_lens, mi_bf16* out,
+                        void* workspace, size_t ws_bytes, int batch, int n_q_heads, int n_kv_heads, int head_dim,
+                        int block_size, float scale, mi_stream stream, const FusedStep* fused) {
   if (!q || !k_cache || !v_cache || !block_table || !context_lens || !out || !workspace) return MI_EINVAL;
   if (n_q_heads <= 0 || batch < 0 || table_stride <= 0) return MI_EINVAL;
   int rc = check_kv8(n_kv_heads, head_dim, block_size);
@@ -545,9 +703,13 @@ extern "C" int mi_paged_attn_decode_fp8kv(const mi_bf16* q, int64_t q_row_stride
     if ((1 << sft) == tpb) tpb_shift = sft;
   const dim3 grid(nsplit, n_kv_heads, batch);
   hipStream_t st = S(stream);
-#define LAUNCH_DEC8(GG)                                                                                                 \
-  hipLaunchKernelGGL(paged_attn_decode_fp8kv_kernel<GG>, grid, dim3(512), 0, st, q, q_row_stride, k_cache, v_cache,       \
-                     block_table, table_stride, context_lens, part_o, part_ml, out, n_q_heads, tpb, tpb_shift, sl2)
+  const FusedStep fs = fused ? *fused : FusedStep{};
+#define LAUNCH_DEC8_AS(GG, FF)                                                                                          \
+  hipLaunchKernelGGL((paged_attn_decode_fp8kv_kernel<GG, FF>), grid, dim3(512), 0, st, q, q_row_stride, k_cache, v_cache, \
+                     block_table, table_stride, context_lens, part_o, part_ml, out, n_q_heads, tpb, tpb_shift, sl2, fs)
+#define LAUNCH_DEC8(GG)                   \
+  if (fused) LAUNCH_DEC8_AS(GG, true);    \
+  else LAUNCH_DEC8_AS(GG, false)
   switch (G) {
     case 1: LAUNCH_DEC8(1); break;
     case 2: LAUNCH_DEC8(2); break;
@@ -556,9 +718,36 @@ extern "C" int mi_paged_attn_decode_fp8kv(const mi_bf16* q, int64_t q_row_stride
     default: LAUNCH_DEC8(16); break;
   }
 #undef LAUNCH_DEC8
+#undef LAUNCH_DEC8_AS
   rc = check_launch();
   if (rc != MI_OK || nsplit == 1) return rc;
   const int rows = batch * n_q_heads;
   hipLaunchKernelGGL(paged_attn_merge_fp8kv_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, part_o, part_ml, out, rows, nsplit);
   return check_launch();
+}
+
+extern "C" int mi_paged_attn_decode_fp8kv(const mi_bf16* q, int64_t q_row_stride, const uint8_t* k_cache,
+                                          const uint8_t* v_cache, const int32_t* block_table, int table_stride,
+                                          const int32_t* context_lens, mi_bf16* out, void* workspace, size_t ws_bytes,
+                                          int batch, int n_q_heads, int n_kv_heads, int head_dim, int block_size,
+                                          float scale, mi_stream stream) {
+  return decode8_impl(q, q_row_stride, k_cache, v_cache, block_table, table_stride, context_lens, out, workspace, ws_bytes,
+                      batch, n_q_heads, n_kv_heads, head_dim, block_size, scale, stream, nullptr);
+}
+
+// qwen3.py:79-90 + attention.py:32-35,63-93 over the fp8 cache: the launches mi_rmsnorm (q), mi_rmsnorm (k), mi_rope,
+// mi_kv_store_fp8 and mi_paged_attn_decode_fp8kv in one
+extern "C" int mi_paged_attn_decode_fp8kv_fused(const mi_bf16* qkv, int64_t qkv_row_stride, const mi_bf16* q_w,
+                                                const mi_bf16* k_w, float eps, const int64_t* positions,
+                                                const float* cos_sin, const int32_t* slot_2d, uint8_t* k_cache,
+                                                uint8_t* v_cache, const int32_t* block_table, int table_stride,
+                                                const int32_t* context_lens, mi_bf16* out, void* workspace,
+                                                size_t ws_bytes, int batch, int n_q_heads, int n_kv_heads, int head_dim,
+                                                int block_size, float scale, mi_stream stream) {
+  if (!positions || !cos_sin || !slot_2d) return MI_EINVAL;
+  if ((q_w == nullptr) != (k_w == nullptr)) return MI_EINVAL;
+  if (!aligned16(cos_sin) || (q_w && (!aligned16(q_w) || !aligned16(k_w)))) return MI_EINVAL;
+  const FusedStep fs{q_w, k_w, positions, cos_sin, slot_2d, eps};
+  return decode8_impl(qkv, qkv_row_stride, k_cache, v_cache, block_table, table_stride, context_lens, out, workspace,
+                      ws_bytes, batch, n_q_heads, n_kv_heads, head_dim, block_size, scale, stream, &fs);
 }

@@ -35,12 +35,15 @@ class Attention(nn.Module):
         # groups of 7 take the module-by-module sequence RoPE -> store -> attention on the same fragment-native kernels
         self.fusable = ops.attention_is_fusable(num_heads, num_kv_heads, head_dim)
         self.kv_scratch = None  # fp8 cache only: (k, v) bf16 scratch of one layer, shared by all layers
+        self.fp8_decode_fusable = False  # fp8 cache only: the geometry takes the fused fp8 decode launch
 
     def set_fp8_cache(self, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_scratch) -> None:
-        """fp8 KV cache: the store is a launch of its own (the fused step prologues write bf16 rows), so the model
-        takes the operator-by-operator sequence norm -> RoPE -> store -> attention."""
+        """fp8 KV cache: prefill takes the operator-by-operator sequence norm -> RoPE -> store -> expand -> attention
+        (the bf16 fused forms write bf16 rows); a decode step of a fusable geometry is one launch
+        (ops.paged_attn_decode_fp8kv_fused, called by the streaming forward of models/qwen3.py)."""
         self.k_cache, self.v_cache, self.kv_scratch = k_cache, v_cache, kv_scratch
         self.fusable = False
+        self.fp8_decode_fusable = ops.attention_is_fusable(self.num_heads, self.num_kv_heads, self.head_dim)
 
     def _store_kvcache(self, k: torch.Tensor, v: torch.Tensor, context) -> None:
         """attention.py:22-35: flat slots in prefill, [block, offset] pairs in decode."""

@@ -298,6 +298,9 @@ class Qwen3Model(nn.Module):
           -> q/k-norm + RoPE + KV store + paged attention in one launch          (mi_paged_attn_decode_fused)
           -> split-K o_proj -> add+RMSNorm -> gate_up GEMM + SwiGLU epilogue -> split-K down_proj.
         MI355_ATTN_FUSED=0 keeps q/k-norm+RoPE+store as its own launch (mi_qknorm_rope_store).
+        With the fp8 KV cache a decode step takes the same single launch over the e4m3 tiles
+        (mi_paged_attn_decode_fp8kv_fused); MI355_ATTN_FUSED=0, and every prefill, run q-norm, k-norm, RoPE, the
+        quantising store and the attention as launches of their own.
         With tensor parallelism the two row-parallel projections produce bf16 partial sums as complete
         rows (mi_gemm_bf16_rows4); the all-reduce over the ranks (linear.py:149-153) and the following
         add+RMSNorm are ONE launch over xGMI (mi_allreduce_add_rmsnorm), or RCCL all-reduce + add+RMSNorm
@@ -317,7 +320,10 @@ class Qwen3Model(nn.Module):
                       and os.environ.get("MI355_XGMI_FUSED", "1") != "0")
 
         def attend(attn, qkv):
-            if not attn.attn.fusable:  # head_dim 64 / groups of 7 / the plain-layout family: one launch per operator
+            fp8_step = fuse_attn and attn.attn.fp8_decode_fusable  # fp8 KV cache: decode steps only
+            if not attn.attn.fusable and not fp8_step:
+                # head_dim 64 / groups of 7 / the plain-layout family / the fp8 cache outside the fused decode step:
+                # one launch per operator
                 return attn._attend_unfused(positions, qkv).flatten(1, -1)
             if not fuse_attn:
                 return attn._attend_fused(positions, qkv)
@@ -327,10 +333,10 @@ class Qwen3Model(nn.Module):
                 rope.cos_sin_cache = rope.cos_sin_cache.to(qkv.device)
             qw = attn.q_norm.weight if attn.qk_norm else None
             kw = attn.k_norm.weight if attn.qk_norm else None
-            return ops.paged_attn_decode_fused(qkv, qw, kw, attn.rms_norm_eps, positions, rope.cos_sin_cache,
-                                               ctx.slot_mapping, a.k_cache, a.v_cache, ctx.block_tables,
-                                               ctx.context_lens, attn.num_heads, attn.num_kv_heads, ctx.block_size,
-                                               a.scale)
+            step = ops.paged_attn_decode_fp8kv_fused if fp8_step else ops.paged_attn_decode_fused
+            return step(qkv, qw, kw, attn.rms_norm_eps, positions, rope.cos_sin_cache, ctx.slot_mapping, a.k_cache,
+                        a.v_cache, ctx.block_tables, ctx.context_lens, attn.num_heads, attn.num_kv_heads,
+                        ctx.block_size, a.scale)
 
         def row_parallel(x, lin):
             """-> (tensor, is_partials): bf16 rows, or fp32 split-K partials for add_rmsnorm_splitk"""

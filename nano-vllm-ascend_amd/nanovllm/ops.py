@@ -155,6 +155,36 @@ def paged_attn_decode_fp8kv(q, k_cache, v_cache, block_tables, context_lens, n_q
     return out
 
 
+def paged_attn_decode_fp8kv_fused(qkv, q_w, k_w, eps: float, positions, cos_sin, slots_2d, k_cache, v_cache, block_tables,
+                                  context_lens, n_q_heads: int, n_kv_heads: int, block_size: int, scale: float,
+                                  out=None, workspace=None) -> torch.Tensor:
+    """paged_attn_decode_fused over an fp8 cache: q/k-norm + RoPE + the quantising store of the step's token + paged
+    decode attention in ONE launch (bit-identical to rmsnorm, rmsnorm, rope, kv_store_fp8, paged_attn_decode_fp8kv)."""
+    require_gpu(qkv, positions, cos_sin, slots_2d, k_cache, v_cache, block_tables, context_lens)
+    _bf16(qkv, q_w, k_w)
+    _fp8_cache(k_cache, v_cache)
+    batch = qkv.shape[0]
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (n_q_heads + 2 * n_kv_heads) * HEAD_DIM
+    assert positions.dtype == torch.int64 and positions.is_contiguous() and positions.numel() == batch
+    assert cos_sin.dtype == torch.float32 and cos_sin.is_contiguous()
+    assert slots_2d.dtype == torch.int32 and slots_2d.is_contiguous() and slots_2d.shape == (batch, 2)
+    assert block_tables.dtype == torch.int32 and block_tables.stride(1) == 1
+    assert context_lens.dtype == torch.int32 and context_lens.is_contiguous()
+    if out is None:
+        out = torch.empty((batch, n_q_heads * HEAD_DIM), dtype=_BF16, device=qkv.device)
+    if workspace is None:
+        workspace = attn_workspace(qkv.device, batch, n_q_heads)
+    check(
+        lib.mi_paged_attn_decode_fp8kv_fused(ptr(qkv), qkv.stride(0), ptr(q_w), ptr(k_w), float(eps), ptr(positions),
+                                             ptr(cos_sin), ptr(slots_2d), ptr(k_cache), ptr(v_cache), ptr(block_tables),
+                                             block_tables.stride(0), ptr(context_lens), ptr(out), ptr(workspace),
+                                             workspace.numel() * workspace.element_size(), batch, n_q_heads, n_kv_heads,
+                                             HEAD_DIM, block_size, float(scale), stream()),
+        "mi_paged_attn_decode_fp8kv_fused",
+    )
+    return out
+
+
 def kv_fp8_supported(n_q_heads: int, n_kv_heads: int, head_dim: int) -> bool:
     """The head geometries the fp8-KV kernels are built for: head_dim 128, GQA groups 1, 2, 4, 8, 16."""
     return head_dim == HEAD_DIM and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8, 16)

@@ -193,6 +193,9 @@ def fp8_kv_attention():
         t = timeit(lambda l: ops.paged_attn_decode_fp8kv(front(l), k8[l], v8[l], perm, ctxl, hq, hkv, bs, 128 ** -0.5, out=out,
                                                          workspace=ws), L)
         print(f"#{rnd} fp8 step (front launches + attention, five launches):          {t * 1e6:7.2f} us")
+        t = timeit(lambda l: ops.paged_attn_decode_fp8kv_fused(qkv, w128, w128, 1e-6, pos, rope_t, sl, k8[l], v8[l], perm, ctxl,
+                                                               hq, hkv, bs, 128 ** -0.5, out=out, workspace=ws), L)
+        print(f"#{rnd} fp8 fused step (norm + RoPE + quantising store + attention, one launch): {t * 1e6:7.2f} us")
 
 
 def head_and_sampler():
