@@ -81,9 +81,9 @@ constexpr int x_slab_bytes(int MT) { return MT * 16 * 64 * 2; }
 // that no load is conditional and hipcc's wait counts stay exact (vmcnt = the loads of the newer block).
 template <int MT, int RT, int WAVES, int STEPS, int WF, int EPI, bool BIAS, bool STAMP = false, bool PIPE = false>
 __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_kernel(
-    const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, const uint16_t* __restrict__ bias,
-    uint16_t* __restrict__ y, float* __restrict__ part, const float* __restrict__ scale, int M_all, int N, int K,
-    PickArgs pk, unsigned long long* __restrict__ stamps = nullptr) {
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, int M_all, int N, int K, int kslice,
+    const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, float* __restrict__ part,
+    const float* __restrict__ scale, PickArgs pk, unsigned long long* __restrict__ stamps = nullptr) {
   unsigned long long ts[8] = {};
 #define MI_GSTAMP(i)                                    \
   do {                                                  \
@@ -108,8 +108,9 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r = lane & 15;
   uint16_t* slab = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(red) + wave * SLOT);
-  const int ksplit = gridDim.y;
-  const int kslice = K / (ksplit * WAVES);  // multiple of 32 * STEPS (checked on the host)
+  // kslice = K / (gridDim.y * WAVES), a multiple of 32 * STEPS, computed and checked on the host: with x, w and the sizes
+  // it is in the argument prefix that arrives in SGPRs (kernarg preload, see the Makefile), so the first weight and
+  // activation addresses need no load of the kernarg segment - gridDim would be one - and no scalar division
   const int kbeg = (blockIdx.y * WAVES + wave) * kslice;
   const int ktiles = K >> 5;
 
@@ -696,7 +697,7 @@ static bool launch_stamped(const GemmArgs& a, unsigned long long* stamps) {
   do {                                                                                                              \
     const size_t slot = (size_t)RT * MT * 1024 > (size_t)x_slab_bytes(MT) ? (size_t)RT * MT * 1024 : (size_t)x_slab_bytes(MT); \
     hipLaunchKernelGGL((gemm_skinny_kernel<MT, RT, W, 2, 1, EPI, false, true>), grid, dim3(W * 64), W * slot, a.st, \
-                       a.x, a.w, a.bias, a.y, a.part, a.scale, a.M, a.N, a.K, a.pick, stamps);                      \
+                       a.x, a.w, a.M, a.N, a.K, a.K / (a.ksplit * W), a.bias, a.y, a.part, a.scale, a.pick, stamps); \
     return true;                                                                                                    \
   } while (0)
   if (waves == 16) MI_STAMPED_GO(16);
@@ -710,14 +711,14 @@ template <int MT, int RT, int WAVES, int STEPS, int WF, int EPI, bool PIPE = fal
 static void launch(const GemmArgs& a) {
   const size_t slot = (size_t)RT * MT * 1024 > (size_t)x_slab_bytes(MT) ? (size_t)RT * MT * 1024 : (size_t)x_slab_bytes(MT);
   const size_t lds = (size_t)WAVES * slot;
-  const int tiles = a.N / 16;
+  const int tiles = a.N / 16, kslice = a.K / (a.ksplit * WAVES);
   const dim3 grid(EPI == EPI_SILU ? tiles / 2 : tiles / RT, a.ksplit, (a.M + kSkinnyRows - 1) / kSkinnyRows);
   if (a.bias && EPI == EPI_NONE)
     hipLaunchKernelGGL((gemm_skinny_kernel<MT, RT, WAVES, STEPS, WF, EPI, true, false, PIPE>), grid, dim3(WAVES * 64), lds,
-                       a.st, a.x, a.w, a.bias, a.y, a.part, a.scale, a.M, a.N, a.K, a.pick, nullptr);
+                       a.st, a.x, a.w, a.M, a.N, a.K, kslice, a.bias, a.y, a.part, a.scale, a.pick, nullptr);
   else
     hipLaunchKernelGGL((gemm_skinny_kernel<MT, RT, WAVES, STEPS, WF, EPI, false, false, PIPE>), grid, dim3(WAVES * 64), lds,
-                       a.st, a.x, a.w, a.bias, a.y, a.part, a.scale, a.M, a.N, a.K, a.pick, nullptr);
+                       a.st, a.x, a.w, a.M, a.N, a.K, kslice, a.bias, a.y, a.part, a.scale, a.pick, nullptr);
 }
 
 // choose STEPS (k-steps in flight per wave and iteration) from the K-slice and the register budget

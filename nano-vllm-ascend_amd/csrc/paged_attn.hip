@@ -251,10 +251,12 @@ __device__ __forceinline__ void patch_new_token(u32x4 (&K)[4], u32x4 (&V)[4], co
 // instrumented instantiation is a separate kernel; the product kernels carry no stamp code.
 template <int G, int WAVES, bool FUSE, bool PIPE, bool STAMP = false, int DB = 4>
 __global__ __launch_bounds__(WAVES * 64) void paged_attn_decode_kernel(
-    const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* kc,
-    const uint16_t* vc, const int32_t* __restrict__ block_table, int table_stride,
-    const int32_t* __restrict__ ctx_lens, float* __restrict__ part_o, float* __restrict__ part_ml,
-    uint16_t* __restrict__ out, int n_q_heads, KvStrides kvs, int tpb, int tpb_shift, int resolve_run, float scale_log2e, FusedStep fs,
+    // the first 14 dwords arrive in SGPRs at wave start (kernarg preload, see the Makefile): everything between the
+    // entry and the first K/V request that heads a chain of dependent loads.  `splits` = gridDim.x.
+    const int32_t* __restrict__ ctx_lens, const int32_t* __restrict__ block_table, int table_stride, int splits,
+    const uint16_t* kc, const uint16_t* vc, int tpb, int tpb_shift, int resolve_run, int n_q_heads,
+    const uint16_t* __restrict__ q, int64_t q_stride, float* __restrict__ part_o, float* __restrict__ part_ml,
+    uint16_t* __restrict__ out, KvStrides kvs, float scale_log2e, FusedStep fs,
     unsigned long long* __restrict__ stamps = nullptr) {
   static_assert(!FUSE || PIPE, "the fused prologue needs the register room of the 8-wave form");
   static_assert(!FUSE || DB == 4, "the fused step prologue is written for 128-wide heads");
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(WAVES * 64) void paged_attn_decode_kernel(
   __shared__ __attribute__((aligned(16))) uint16_t sm_q[PIPE ? G : 1][D];
   __shared__ __attribute__((aligned(16))) uint16_t sm_k[FUSE ? 128 : 8], sm_v[FUSE ? 128 : 8];  // the step's new K / V row
 
-  const int split = blockIdx.x, splits = gridDim.x, h = blockIdx.y, b = blockIdx.z;
+  const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int ctx = max(ctx_lens[b], 0);
   const int n_tiles = (ctx + 15) >> 4;
   // the context is cut into chunks of two 16-token tiles (only the very last chunk may hold one);
@@ -1081,18 +1083,18 @@ static int decode_impl(const mi_bf16* q, int64_t q_row_stride, const mi_bf16* k_
   hipStream_t st = S(stream);
   const FusedStep fs = fused ? *fused : FusedStep{};
 #define LAUNCH_DEC_AS(GG, WW, FF, PP, DD)                                                                            \
-  hipLaunchKernelGGL((paged_attn_decode_kernel<GG, WW, FF, PP, false, DD>), grid, dim3(WW * 64), 0, st, q,            \
-                     q_row_stride, k_cache, v_cache, block_table, table_stride, context_lens, part_o, part_ml, out, \
-                     n_q_heads, kvs, block_size / 16, tpb_shift, resolve_run, sl2, fs)
+  hipLaunchKernelGGL((paged_attn_decode_kernel<GG, WW, FF, PP, false, DD>), grid, dim3(WW * 64), 0, st, context_lens, \
+                     block_table, table_stride, nsplit, k_cache, v_cache, block_size / 16, tpb_shift, resolve_run,   \
+                     n_q_heads, q, q_row_stride, part_o, part_ml, out, kvs, sl2, fs)
 #define LAUNCH_DEC(GG, WW)                              \
   if (fused) LAUNCH_DEC_AS(GG, 8, true, true, 4);       \
   else if (pipe) LAUNCH_DEC_AS(GG, 8, false, true, 4);  \
   else LAUNCH_DEC_AS(GG, WW, false, false, 4)
   if (stamps != nullptr) {  // the instrumented kernel: the bench model's geometry only
     if (!fused || G != 2) return MI_EUNSUPPORTED;
-    hipLaunchKernelGGL((paged_attn_decode_kernel<2, 8, true, true, true>), grid, dim3(8 * 64), 0, st, q, q_row_stride,
-                       k_cache, v_cache, block_table, table_stride, context_lens, part_o, part_ml, out, n_q_heads, kvs,
-                       block_size / 16, tpb_shift, resolve_run, sl2, fs, stamps);
+    hipLaunchKernelGGL((paged_attn_decode_kernel<2, 8, true, true, true>), grid, dim3(8 * 64), 0, st, context_lens,
+                       block_table, table_stride, nsplit, k_cache, v_cache, block_size / 16, tpb_shift, resolve_run,
+                       n_q_heads, q, q_row_stride, part_o, part_ml, out, kvs, sl2, fs, stamps);
     rc = check_launch();
     if (rc != MI_OK || nsplit == 1) return rc;
     hipLaunchKernelGGL(paged_attn_merge_kernel<128>, dim3((batch * n_q_heads + 3) / 4), dim3(256), 0, st, part_o, part_ml,
