@@ -80,7 +80,8 @@ enum mi_tuning_knob {
   MI_TUNE_NORM_WPR = 2,           /* mi_add_rmsnorm_splitk: waves per row for <= 64 rows: 4 (default), 2, 1                     */
   MI_TUNE_ROPE_BLOCK64 = 3,       /* mi_qknorm_rope_store: one-wave workgroups for <= 64 tokens (default 1)                     */
   MI_TUNE_PLAIN_SPLIT_TARGET = 4, /* mi_paged_attn_decode_plain: workgroups aimed for when contexts are split (default 512)     */
-  MI_TUNE_PREFILL_P_SPLIT = 5,    /* prefill attention: probabilities as bf16 hi + lo (1) instead of one bf16 (default 0)       */
+  MI_TUNE_PREFILL_P_SPLIT = 5,    /* prefill attention: probabilities as bf16 hi + lo (1) instead of one bf16 (default 0);
+                                     the bf16-cache kernels only - mi_paged_attn_prefill_fp8kv[_fused] always take one bf16     */
   MI_TUNE_GEMM_PIPE = 6,          /* streaming GEMMs: double-buffered K loop for K-slices of two or more blocks (default 1)     */
   MI_TUNE_COUNT = 7
 };
@@ -176,6 +177,40 @@ int mi_paged_attn_decode_fp8kv_fused(const mi_bf16* qkv, int64_t qkv_row_stride,
 int mi_kv_fp8_expand(const uint8_t* k_cache, const uint8_t* v_cache, mi_bf16* k_scratch, mi_bf16* v_scratch,
                      const int32_t* block_table, int table_stride, const int32_t* kv_lens, int n_seqs,
                      int n_kv_heads, int head_dim, int block_size, mi_stream stream);
+
+/* mi_paged_attn_prefill over an fp8 cache (attention.py:37-62; same arguments with uint8_t caches, same result contract
+ * as the fp8 decode kernel: causal GQA attention over the dequantised rows, P as one bf16 per key).  The e4m3 tiles are
+ * read as stored and dequantised in registers - no bf16 scratch, no mi_kv_fp8_expand in front.  kv_lens[s] >= q_len of
+ * sequence s (cached prefixes).  Keys that are masked (causal, past kv_lens, the tail of a partial tile) contribute
+ * exactly nothing whatever finite bytes and scales their slots hold.  n_q_heads / n_kv_heads in {1, 2, 4, 8, 16},
+ * head_dim 128, any block_size that is a multiple of 16; MI_TUNE_PREFILL_P_SPLIT does not apply. */
+int mi_paged_attn_prefill_fp8kv(const mi_bf16* q, int64_t q_row_stride,
+                                const uint8_t* k_cache, const uint8_t* v_cache,
+                                const int32_t* block_table, int table_stride,
+                                const int32_t* cu_seqlens_q, const int32_t* kv_lens, int n_seqs, int max_seqlen_q,
+                                mi_bf16* out, int n_q_heads, int n_kv_heads, int head_dim,
+                                int block_size, float scale, mi_stream stream);
+
+/* mi_paged_attn_prefill_fused over an fp8 cache (qwen3.py:83-88 for the queries + attention.py:37-62): qkv points at
+ * the packed qkv rows, per-head RMSNorm with q_w (NULL: none) and NeoX RoPE run while the Q operand is loaded.  The
+ * output is bit-identical to mi_paged_attn_prefill_fp8kv over the q rows mi_qknorm_rope_store writes. */
+int mi_paged_attn_prefill_fp8kv_fused(const mi_bf16* qkv, int64_t qkv_row_stride, const mi_bf16* q_w, float eps,
+                                      const int64_t* positions, const float* cos_sin,
+                                      const uint8_t* k_cache, const uint8_t* v_cache,
+                                      const int32_t* block_table, int table_stride,
+                                      const int32_t* cu_seqlens_q, const int32_t* kv_lens, int n_seqs, int max_seqlen_q,
+                                      mi_bf16* out, int n_q_heads, int n_kv_heads, int head_dim,
+                                      int block_size, float scale, mi_stream stream);
+
+/* The K / V front of a prefill step over an fp8 cache in one launch (qwen3.py:83-88 for the keys + attention.py:22-35):
+ * from the packed qkv rows, k-norm (k_w, NULL: none), RoPE on K and the quantising store of K and V at the flat slots
+ * slot_flat[t] (negative: skipped).  Every cache byte and scale is bit-identical to mi_rmsnorm (k) -> mi_rope ->
+ * mi_kv_store_fp8; 16 consecutive tokens that fill one aligned tile leave as whole tiles.  The query columns are not
+ * touched (mi_paged_attn_prefill_fp8kv_fused prepares them). */
+int mi_qknorm_rope_store_fp8(const mi_bf16* qkv, int64_t qkv_row_stride, const mi_bf16* k_w, float eps,
+                             const int64_t* positions, const float* cos_sin,
+                             uint8_t* k_cache, uint8_t* v_cache, const int32_t* slot_flat, int n_tokens,
+                             int n_q_heads, int n_kv_heads, int head_dim, int block_size, mi_stream stream);
 
 /* Test/debug helper: rows of an fp8 cache in logical layout - out_q [n, n_kv_heads*128] e4m3 bytes and out_scale
  * [n, n_kv_heads] fp32, one row per flat slot (negative: zeros). */

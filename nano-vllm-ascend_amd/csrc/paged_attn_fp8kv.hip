@@ -31,47 +31,15 @@
 
 #include "mi_common.hpp"
 #include "kv_store.hpp"
+#include "kv8_common.hpp"
 #include "prefill_common.hpp"
 #include "step_prologue.hpp"
 
 namespace mi {
 
-constexpr int KV8_DATA = 2048;              // e4m3 bytes of a tile; the scales follow
-constexpr int KV8_TILE = MI_KV8_TILE_BYTES;
+// (the tile's addressing, dq4 / dq8, the quantisation rule and check_kv8: kv8_common.hpp, shared with the prefill
+// kernels of prefill_fp8kv.hip)
 typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-// byte offset of (t, d) inside a K / V tile
-__host__ __device__ __forceinline__ int k8_tile_off(int t, int d) {
-  return (d >> 6) * 1024 + ((((d >> 3) & 3) * 16 + t) << 4) + ((d >> 5) & 1) * 8 + (d & 7);
-}
-__host__ __device__ __forceinline__ int v8_tile_off(int t, int d) {
-  return (d >> 6) * 1024 + ((((t >> 2) * 16) + (d & 15)) << 4) + ((d >> 4) & 3) * 4 + (t & 3);
-}
-__host__ __device__ __forceinline__ int64_t kv8_tile_base(int64_t blk, int h, int slot_in_block, int n_kv_heads, int tpb) {
-  return ((blk * n_kv_heads + h) * tpb + (slot_in_block >> 4)) * (int64_t)KV8_TILE;
-}
-
-// four e4m3 -> four bf16 (exact: the upper halves of the fp32 conversions)
-__device__ __forceinline__ u32x2 dq4(uint32_t w) {
-  const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
-  return u32x2{__builtin_amdgcn_perm(__float_as_uint(lo[1]), __float_as_uint(lo[0]), 0x07060302u),
-               __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u)};
-}
-__device__ __forceinline__ bf16x8 dq8(uint32_t w0, uint32_t w1) {
-  const u32x2 a = dq4(w0), b = dq4(w1);
-  return as_frag(u32x4{a[0], a[1], b[0], b[1]});
-}
-
-// The quantisation rule, shared by the store kernel and the fused decode step.  floor(log2 amax) is the exponent field
-// (a bf16 subnormal maximum falls under the clamp in any case).
-__device__ __forceinline__ int kv8_exponent(float amax) {
-  return amax == 0.f ? 0 : max((int)(__float_as_uint(amax) >> 23) - 127 - 7, -120);
-}
-// four values times 2^-e -> four e4m3 bytes, the first in the low byte
-__device__ __forceinline__ uint32_t quant4(float a, float b, float c, float d, float inv) {
-  const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a * inv, b * inv, 0, false);
-  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c * inv, d * inv, w, true);
-}
 
 // ---------------------------------------------------------------------------
 // store: 8 lanes per (token, kv head, K | V) row, 16 values each (dims 8 j .. and 64 + 8 j ..)
@@ -624,12 +592,6 @@ static int decode_splits8(int batch, int n_kv_heads) {
   const int base = batch * n_kv_heads * 16;
   const int ns = 4096 / (base > 0 ? base : 1);
   return ns < 1 ? 1 : (ns > 16 ? 16 : ns);
-}
-
-static int check_kv8(int n_kv_heads, int head_dim, int block_size) {
-  if (n_kv_heads <= 0) return MI_EINVAL;
-  if (head_dim != MI_HEAD_DIM || block_size <= 0 || block_size % 16) return MI_EUNSUPPORTED;
-  return MI_OK;
 }
 
 }  // namespace mi

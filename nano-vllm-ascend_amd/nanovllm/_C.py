@@ -69,6 +69,19 @@ _SIGNATURES = {
          c_int, c_int, c_float, _p],
     ),
     "mi_kv_fp8_expand": (c_int, [_p, _p, _p, _p, _p, c_int, _p, c_int, c_int, c_int, c_int, _p]),
+    "mi_paged_attn_prefill_fp8kv": (
+        c_int,
+        [_p, c_int64, _p, _p, _p, c_int, _p, _p, c_int, c_int, _p, c_int, c_int, c_int, c_int, c_float, _p],
+    ),
+    "mi_paged_attn_prefill_fp8kv_fused": (
+        c_int,
+        [_p, c_int64, _p, c_float, _p, _p, _p, _p, _p, c_int, _p, _p, c_int, c_int, _p, c_int, c_int, c_int, c_int,
+         c_float, _p],
+    ),
+    "mi_qknorm_rope_store_fp8": (
+        c_int,
+        [_p, c_int64, _p, c_float, _p, _p, _p, _p, _p, c_int, c_int, c_int, c_int, c_int, _p],
+    ),
     "mi_kv_cache_gather_fp8": (c_int, [_p, c_int, _p, c_int, _p, _p, c_int, c_int, c_int, _p]),
     "mi_paged_attn_decode_workspace": (c_size_t, [c_int, c_int]),
     "mi_paged_attn_decode": (

@@ -369,9 +369,13 @@ class ModelRunner:
         layers = hf.num_hidden_layers
         block_bytes = 2 * layers * self.block_size * n_kv * head_dim * 2
         fp8 = cfg.kv_cache_dtype == "fp8"
-        if fp8:  # e4m3 data + scales in every layer, and the block's share of the one-layer bf16 prefill scratch
-            block_bytes = (2 * layers * (self.block_size // 16) * n_kv * KV8_TILE_BYTES
-                           + 2 * self.block_size * n_kv * head_dim * 2)
+        # MI355_FP8_PREFILL=expand: the fp8 prefill dequantises the step's blocks into a one-layer bf16 scratch and runs
+        # the bf16 kernel over it (the first form, kept for A/B); default: prefill attends the e4m3 tiles, no scratch
+        fp8_expand = fp8 and os.environ.get("MI355_FP8_PREFILL", "direct") == "expand"
+        if fp8:  # e4m3 data + scales in every layer (+ under `expand` the block's share of the scratch)
+            block_bytes = 2 * layers * (self.block_size // 16) * n_kv * KV8_TILE_BYTES
+            if fp8_expand:
+                block_bytes += 2 * self.block_size * n_kv * head_dim * 2
         if cfg.num_kvcache_blocks <= 0:
             available = total * cfg.gpu_memory_utilization - used - peak + current
             cfg.num_kvcache_blocks = int(available) // block_bytes
@@ -394,9 +398,11 @@ class ModelRunner:
         if fp8:
             self.kv_cache = torch.zeros((2, layers, *ops.kv_cache_shape_fp8(alloc_blocks, n_kv, self.block_size)),
                                         dtype=torch.uint8, device=self.device)
-            self.kv_scratch = torch.zeros((2, *ops.kv_cache_shape(alloc_blocks, n_kv, self.block_size, head_dim)),
-                                          dtype=torch.bfloat16, device=self.device)
-            scratch = (self.kv_scratch[0, : cfg.num_kvcache_blocks], self.kv_scratch[1, : cfg.num_kvcache_blocks])
+            self.kv_scratch, scratch = None, None
+            if fp8_expand:
+                self.kv_scratch = torch.zeros((2, *ops.kv_cache_shape(alloc_blocks, n_kv, self.block_size, head_dim)),
+                                              dtype=torch.bfloat16, device=self.device)
+                scratch = (self.kv_scratch[0, : cfg.num_kvcache_blocks], self.kv_scratch[1, : cfg.num_kvcache_blocks])
             layer_id = 0
             for module in self.model.modules():
                 if hasattr(module, "k_cache") and hasattr(module, "v_cache"):

@@ -99,9 +99,39 @@ class Qwen3Attention(nn.Module):
         qkv = self.qkv_proj(hidden_states)
         if self.fused and self.attn.k_cache.numel() > 0 and self.attn.fusable:
             o = self._attend_fused(positions, qkv)
+        elif self._fp8_prefill_takes(qkv):
+            o = self._attend_fp8_prefill(positions, qkv)
         else:
             o = self._attend_unfused(positions, qkv)
         return self.o_proj(o.flatten(1, -1))
+
+    def _fp8_prefill_takes(self, qkv: torch.Tensor) -> bool:
+        """A prefill step over the fp8 KV cache that runs as two launches: at least 64 tokens, the e4m3 tiles attended
+        directly (no MI355_FP8_PREFILL=expand scratch), MI355_PREFILL_FUSED_Q not "0"."""
+        ctx, attn = get_context(), self.attn
+        return (self.fused and attn.fp8 and attn.kv_scratch is None and attn.fp8_decode_fusable and ctx.is_prefill
+                and qkv.is_cuda and qkv.dim() == 2 and qkv.shape[0] >= 64 and ctx.slot_mapping.dim() == 1
+                and os.environ.get("MI355_PREFILL_FUSED_Q", "1") != "0")
+
+    def _attend_fp8_prefill(self, positions: torch.Tensor, qkv: torch.Tensor) -> torch.Tensor:
+        """k-norm + RoPE + the quantising K / V store (mi_qknorm_rope_store_fp8), then the attention over the e4m3 tiles
+        with q-norm + RoPE in its Q-operand load (mi_paged_attn_prefill_fp8kv_fused): two launches for the six of
+        _attend_unfused over the expansion scratch."""
+        ctx, attn, rope = get_context(), self.attn, self.rotary_emb
+        attn.block_size = ctx.block_size
+        if rope.cos_sin_cache.device != qkv.device:
+            rope.cos_sin_cache = rope.cos_sin_cache.to(qkv.device)
+        qw = self.q_norm.weight if self.qk_norm else None
+        kw = self.k_norm.weight if self.qk_norm else None
+        ops.qknorm_rope_store_fp8(qkv, kw, self.rms_norm_eps, positions, rope.cos_sin_cache, attn.k_cache, attn.v_cache,
+                                  ctx.slot_mapping, self.num_heads, self.num_kv_heads, ctx.block_size)
+        kv_lens = ctx.kv_lens
+        if kv_lens is None:
+            kv_lens = (ctx.cu_seqlens_k[1:] - ctx.cu_seqlens_k[:-1]).contiguous()
+        return ops.paged_attn_prefill_fp8kv_fused(qkv, qw, self.rms_norm_eps, positions, rope.cos_sin_cache, attn.k_cache,
+                                                  attn.v_cache, ctx.block_tables, ctx.cu_seqlens_q, kv_lens,
+                                                  ctx.max_seqlen_q, self.num_heads, self.num_kv_heads, ctx.block_size,
+                                                  attn.scale)
 
     def _attend_unfused(self, positions: torch.Tensor, qkv: torch.Tensor) -> torch.Tensor:
         """The reference's operator sequence (qwen3.py:79-90): split, per-head q/k norm, RoPE, store + attention - one
@@ -299,7 +329,8 @@ class Qwen3Model(nn.Module):
           -> split-K o_proj -> add+RMSNorm -> gate_up GEMM + SwiGLU epilogue -> split-K down_proj.
         MI355_ATTN_FUSED=0 keeps q/k-norm+RoPE+store as its own launch (mi_qknorm_rope_store).
         With the fp8 KV cache a decode step takes the same single launch over the e4m3 tiles
-        (mi_paged_attn_decode_fp8kv_fused); MI355_ATTN_FUSED=0, and every prefill, run q-norm, k-norm, RoPE, the
+        (mi_paged_attn_decode_fp8kv_fused) and a prefill of at least 64 tokens two (mi_qknorm_rope_store_fp8,
+        mi_paged_attn_prefill_fp8kv_fused); MI355_ATTN_FUSED=0 and shorter prefills run q-norm, k-norm, RoPE, the
         quantising store and the attention as launches of their own.
         With tensor parallelism the two row-parallel projections produce bf16 partial sums as complete
         rows (mi_gemm_bf16_rows4); the all-reduce over the ranks (linear.py:149-153) and the following
@@ -321,8 +352,10 @@ class Qwen3Model(nn.Module):
 
         def attend(attn, qkv):
             fp8_step = fuse_attn and attn.attn.fp8_decode_fusable  # fp8 KV cache: decode steps only
+            if attn._fp8_prefill_takes(qkv):  # fp8 KV cache, a prefill of 64 .. PREFILL_STREAM_MAX tokens: two launches
+                return attn._attend_fp8_prefill(positions, qkv)
             if not attn.attn.fusable and not fp8_step:
-                # head_dim 64 / groups of 7 / the plain-layout family / the fp8 cache outside the fused decode step:
+                # head_dim 64 / groups of 7 / the plain-layout family / the fp8 cache outside its fused forms:
                 # one launch per operator
                 return attn._attend_unfused(positions, qkv).flatten(1, -1)
             if not fuse_attn:

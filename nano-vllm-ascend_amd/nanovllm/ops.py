@@ -185,6 +185,81 @@ def paged_attn_decode_fp8kv_fused(qkv, q_w, k_w, eps: float, positions, cos_sin,
     return out
 
 
+def paged_attn_prefill_fp8kv(q, k_cache, v_cache, block_tables, cu_seqlens_q, kv_lens, max_seqlen_q: int,
+                             n_q_heads: int, n_kv_heads: int, block_size: int, scale: float, out=None) -> torch.Tensor:
+    """paged_attn_prefill over an fp8 cache: the e4m3 tiles are read as stored (no bf16 scratch, no kv_fp8_expand)."""
+    require_gpu(q, k_cache, v_cache, block_tables, cu_seqlens_q, kv_lens)
+    _bf16(q)
+    _fp8_cache(k_cache, v_cache)
+    T = q.shape[0]
+    q2 = q.view(T, -1) if q.dim() == 3 else q
+    assert q2.stride(1) == 1 and q2.shape[1] == n_q_heads * HEAD_DIM
+    assert block_tables.dtype == torch.int32 and block_tables.stride(1) == 1
+    assert cu_seqlens_q.dtype == torch.int32 and kv_lens.dtype == torch.int32
+    n_seqs = cu_seqlens_q.numel() - 1
+    assert kv_lens.numel() == n_seqs and block_tables.shape[0] >= n_seqs
+    if out is None:
+        out = torch.empty((T, n_q_heads * HEAD_DIM), dtype=_BF16, device=q.device)
+    check(
+        lib.mi_paged_attn_prefill_fp8kv(ptr(q2), q2.stride(0), ptr(k_cache), ptr(v_cache), ptr(block_tables),
+                                        block_tables.stride(0), ptr(cu_seqlens_q), ptr(kv_lens), n_seqs,
+                                        int(max_seqlen_q), ptr(out), n_q_heads, n_kv_heads, HEAD_DIM, block_size,
+                                        float(scale), stream()),
+        "mi_paged_attn_prefill_fp8kv",
+    )
+    return out
+
+
+def paged_attn_prefill_fp8kv_fused(qkv, q_w, eps: float, positions, cos_sin, k_cache, v_cache, block_tables,
+                                   cu_seqlens_q, kv_lens, max_seqlen_q: int, n_q_heads: int, n_kv_heads: int,
+                                   block_size: int, scale: float, out=None) -> torch.Tensor:
+    """paged_attn_prefill_fp8kv over the RAW q heads of the packed qkv rows: q-norm (q_w may be None) + RoPE happen in
+    the kernel's Q-operand load.  K / V must already be cached (qknorm_rope_store_fp8)."""
+    require_gpu(qkv, positions, cos_sin, k_cache, v_cache, block_tables, cu_seqlens_q, kv_lens)
+    _bf16(qkv, q_w)
+    _fp8_cache(k_cache, v_cache)
+    T = qkv.shape[0]
+    assert qkv.stride(1) == 1 and qkv.shape[1] == (n_q_heads + 2 * n_kv_heads) * HEAD_DIM
+    assert positions.dtype == torch.int64 and positions.is_contiguous() and positions.numel() == T
+    assert cos_sin.dtype == torch.float32 and cos_sin.is_contiguous()
+    assert block_tables.dtype == torch.int32 and block_tables.stride(1) == 1
+    assert cu_seqlens_q.dtype == torch.int32 and kv_lens.dtype == torch.int32
+    n_seqs = cu_seqlens_q.numel() - 1
+    assert kv_lens.numel() == n_seqs and block_tables.shape[0] >= n_seqs
+    if out is None:
+        out = torch.empty((T, n_q_heads * HEAD_DIM), dtype=_BF16, device=qkv.device)
+    check(
+        lib.mi_paged_attn_prefill_fp8kv_fused(ptr(qkv), qkv.stride(0), ptr(q_w), float(eps), ptr(positions),
+                                              ptr(cos_sin), ptr(k_cache), ptr(v_cache), ptr(block_tables),
+                                              block_tables.stride(0), ptr(cu_seqlens_q), ptr(kv_lens), n_seqs,
+                                              int(max_seqlen_q), ptr(out), n_q_heads, n_kv_heads, HEAD_DIM, block_size,
+                                              float(scale), stream()),
+        "mi_paged_attn_prefill_fp8kv_fused",
+    )
+    return out
+
+
+def qknorm_rope_store_fp8(qkv, k_w, eps: float, positions, cos_sin, k_cache, v_cache, slots, n_q_heads: int,
+                          n_kv_heads: int, block_size: int) -> None:
+    """The K / V front of an fp8 prefill step: k-norm (k_w may be None) + RoPE on K and the quantising store of K and V
+    at the flat `slots`, from the packed qkv rows (the bytes of rmsnorm, rope, kv_store_fp8).  The queries are left to
+    paged_attn_prefill_fp8kv_fused."""
+    require_gpu(qkv, positions, cos_sin, k_cache, v_cache, slots)
+    _bf16(qkv, k_w)
+    _fp8_cache(k_cache, v_cache)
+    T = qkv.shape[0]
+    assert qkv.stride(1) == 1 and qkv.shape[1] == (n_q_heads + 2 * n_kv_heads) * HEAD_DIM
+    assert positions.dtype == torch.int64 and positions.is_contiguous() and positions.numel() == T
+    assert cos_sin.dtype == torch.float32 and cos_sin.is_contiguous()
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape == (T,)
+    check(
+        lib.mi_qknorm_rope_store_fp8(ptr(qkv), qkv.stride(0), ptr(k_w), float(eps), ptr(positions), ptr(cos_sin),
+                                     ptr(k_cache), ptr(v_cache), ptr(slots), T, n_q_heads, n_kv_heads, HEAD_DIM,
+                                     block_size, stream()),
+        "mi_qknorm_rope_store_fp8",
+    )
+
+
 def kv_fp8_supported(n_q_heads: int, n_kv_heads: int, head_dim: int) -> bool:
     """The head geometries the fp8-KV kernels are built for: head_dim 128, GQA groups 1, 2, 4, 8, 16."""
     return head_dim == HEAD_DIM and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8, 16)

@@ -198,6 +198,64 @@ def fp8_kv_attention():
         print(f"#{rnd} fp8 fused step (norm + RoPE + quantising store + attention, one launch): {t * 1e6:7.2f} us")
 
 
+def fp8_kv_prefill():
+    """The attention side of an fp8-KV prefill layer, six launches over the expansion scratch (q-norm, k-norm, RoPE,
+    quantising store, expand, bf16 attention: MI355_FP8_PREFILL=expand) against the two that read the e4m3 tiles
+    (fused store, fused-Q attention): the bench's prefill step and a prefix-hit step, alternating rounds, plus the
+    pieces on their own (KBENCH_ONLY=fp8kv, or fp8kv_prefill for this part alone)."""
+    n, bs, hq, hkv, L = 16, 16, 16, 8, 4
+    w128 = torch.ones(128, device=DEV).bfloat16()
+    for name, T, ctx in (("prefill step, 16 x 1024 tokens", 1024, 1024), ("prefix hit, 16 x 64 new behind 4032 cached", 64, 4096)):
+        nb = ctx // bs
+        g = torch.Generator(device="cpu").manual_seed(0)
+        k8 = [torch.randint(0, 0x70, ops.kv_cache_shape_fp8(n * nb, hkv, bs), dtype=torch.uint8, device=DEV) for _ in range(L)]
+        v8 = [torch.randint(0, 0x70, ops.kv_cache_shape_fp8(n * nb, hkv, bs), dtype=torch.uint8, device=DEV) for _ in range(L)]
+        for t8 in k8 + v8:
+            t8[..., 2048:].view(torch.float32).fill_(1.0)
+        ks, vs = (torch.zeros(ops.kv_cache_shape(n * nb, hkv, bs), dtype=torch.bfloat16, device=DEV) for _ in range(2))
+        tables = torch.randperm(n * nb, generator=g).to(torch.int32).view(n, nb)
+        pos1 = torch.arange(ctx - T, ctx)
+        slots = (tables[:, pos1 // bs] * bs + pos1 % bs).reshape(-1).int().to(DEV)
+        pos, tables = pos1.repeat(n).to(DEV), tables.to(DEV)
+        qkv = torch.randn(n * T, (hq + 2 * hkv) * 128, device=DEV).bfloat16()
+        q_, k_, v_ = (t.view(n * T, -1, 128) for t in qkv.split([hq * 128, hkv * 128, hkv * 128], dim=-1))
+        fr = torch.arange(ctx).float()[:, None] / (1e6 ** (torch.arange(0, 128, 2).float() / 128))[None]
+        cos_sin = torch.cat([fr.cos(), fr.sin()], -1).to(DEV)
+        out = torch.empty(n * T, hq * 128, dtype=torch.bfloat16, device=DEV)
+        cu = (torch.arange(n + 1, dtype=torch.int32) * T).to(DEV)
+        kvl = torch.full((n,), ctx, dtype=torch.int32, device=DEV)
+        sc = 128 ** -0.5
+
+        def six(l):
+            qr, kr = ops.rope(pos, ops.rmsnorm(q_, w128, 1e-6), ops.rmsnorm(k_, w128, 1e-6), cos_sin, hq, hkv)
+            ops.kv_store_fp8(kr, v_, k8[l], v8[l], slots, hkv, bs)
+            ops.kv_fp8_expand(k8[l], v8[l], ks, vs, tables, kvl, hkv, bs)
+            ops.paged_attn_prefill(qr, ks, vs, tables, cu, kvl, T, hq, hkv, bs, sc, out=out)
+
+        def two(l):
+            ops.qknorm_rope_store_fp8(qkv, w128, 1e-6, pos, cos_sin, k8[l], v8[l], slots, hq, hkv, bs)
+            ops.paged_attn_prefill_fp8kv_fused(qkv, w128, 1e-6, pos, cos_sin, k8[l], v8[l], tables, cu, kvl, T, hq, hkv, bs, sc,
+                                               out=out)
+
+        qr = ops.rope(pos, ops.rmsnorm(q_, w128, 1e-6), ops.rmsnorm(k_, w128, 1e-6), cos_sin, hq, hkv)[0]
+        forms = (("six launches over the scratch", six), ("two launches over the e4m3 tiles", two),
+                 ("  expand alone", lambda l: ops.kv_fp8_expand(k8[l], v8[l], ks, vs, tables, kvl, hkv, bs)),
+                 ("  bf16 attention over the scratch alone",
+                  lambda l: ops.paged_attn_prefill(qr, ks, vs, tables, cu, kvl, T, hq, hkv, bs, sc, out=out)),
+                 ("  fp8kv attention alone (prepared q)",
+                  lambda l: ops.paged_attn_prefill_fp8kv(qr, k8[l], v8[l], tables, cu, kvl, T, hq, hkv, bs, sc, out=out)),
+                 ("  fused fp8 store alone", lambda l: ops.qknorm_rope_store_fp8(qkv, w128, 1e-6, pos, cos_sin, k8[l], v8[l],
+                                                                              slots, hq, hkv, bs)))
+        res = {k: [] for k, _ in forms}
+        for rnd in range(int(os.environ.get("ROUNDS", 4))):
+            for k, fn in forms:
+                res[k].append(round(timeit(fn, L) * 1e6, 1))
+        print(f"fp8-KV prefill, {name} (hq {hq} / hkv {hkv}, block {bs}); us per layer, alternating rounds:")
+        for k, v in res.items():
+            print(f"  {k}: {v}   median {sorted(v)[len(v) // 2]}", flush=True)
+        del k8, v8, ks, vs
+
+
 def head_and_sampler():
     """The head GEMM (151936 x 1024, 32 rows) alone, with the pick epilogue, and the standalone sampler."""
     M, N, K = 32, 151936, 1024
@@ -360,8 +418,11 @@ def main():
         return prefill_attention_order()
     if os.environ.get("KBENCH_ONLY") == "prefill":
         return prefill_attention()
+    if os.environ.get("KBENCH_ONLY") == "fp8kv_prefill":
+        return fp8_kv_prefill()
     if os.environ.get("KBENCH_ONLY") == "fp8kv":
-        return fp8_kv_attention()
+        fp8_kv_attention()
+        return fp8_kv_prefill()
     if os.environ.get("KBENCH_ONLY") == "head":
         return head_and_sampler()
     B, ctx, bs, hq, hkv, L = 32, int(os.environ.get("CTX", 1024)), 16, 16, 8, 28
