@@ -133,7 +133,9 @@ int mi_kv_cache_gather(const mi_bf16* cache, int is_v,
  * a wavefront's 1 KiB load (16 B per lane) dequantises in registers into two MFMA 16x16x32 bf16 operand fragments.
  * Quantisation rule, per (token, kv head) row x[128]: amax = max|x|; e = max(floor(log2 amax) - 7, -120), e = 0 for
  * amax = 0; scale = 2^e; value = RNE_e4m3fn(x / scale).  x / scale and value * scale are exact, so attention over
- * this cache is attention over the dequantised bf16 rows.  Caches must start zero-filled. */
+ * this cache is attention over the dequantised bf16 rows.  (One edge: |x| >= 248 * 2^120 rounds up to 256 * 2^120 =
+ * 2^128, which no bf16 holds - such a value dequantises to inf.  Inf and NaN inputs are outside the rule.)  Caches
+ * must start zero-filled. */
 
 /* Quantise and scatter the step's K / V rows ([n_tokens, n_kv_heads, 128] bf16, row strides in elements).  slots:
  * slot_is_2d = 0: [n_tokens] flat slots (prefill), 1: [n_tokens][2] = {block id, offset} (decode); a negative slot
