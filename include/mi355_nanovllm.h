@@ -597,6 +597,32 @@ int mi_sample(const mi_bf16* logits, int64_t row_stride, const float* temperatur
               int64_t* out, int rows, int vocab, uint64_t seed, uint64_t step,
               mi_stream stream);
 
+/* Top-k / top-p (nucleus) sampling: mi_sample restricted to a kept set of columns per row.  top_k [rows] int32
+ * (<= 0: off), top_p [rows] fp32 (>= 1: off).  All comparisons are on the float values (-0.0 equals +0.0):
+ *   - a row whose temperature is <= 0 gets the lowest column of its maximum, as mi_argmax;
+ *   - top-k: kappa = the k-th largest value counted with multiplicity, V_k = {c : l_c >= kappa} (ties at the threshold
+ *     are all kept; k >= vocab keeps everything);
+ *   - top-p over the survivors of top-k: w_c = exp((l_c - max) / T), W = sum of w over V_k, pi = the largest value v
+ *     with sum{w_c : c in V_k, l_c >= v} >= p * W, V = {c in V_k : l_c >= pi} - the smallest value-threshold set of
+ *     mass >= p, ties kept (the mass is summed in 64-bit fixed point, in no particular order: the same inputs give the
+ *     same token on every run);
+ *   - out[row] = argmax over c in V of the key mi_sample forms for (seed, step, row, c), lowest column on equal keys:
+ *     mi_sample over the logits with every column outside V at -inf, bit for bit.
+ * A row with truncation off (top_k <= 0 and top_p >= 1) is NOT written: out[row] keeps what the step's own pick left
+ * there, and the row costs nothing - the engine launches this once behind a step's token choice when any sequence of
+ * the step truncates.  NaN logits are unspecified, as in mi_sample.  MI_EINVAL: a null pointer, rows or vocab <= 0,
+ * row_stride < vocab; MI_EUNSUPPORTED: row_stride % 8 or logits not 16-byte aligned.
+ * mi_sample_truncated_rng reads {seed, step} from DEVICE memory (the pair the pick epilogue below reads), so the launch
+ * can follow a replayed graph without the host knowing which step it sampled with.
+ * Not available under tensor parallelism (the ranks hold vocabulary shards and the step record of engine/rpc.py does
+ * not carry the two fields): LLMEngine.add_request raises NotImplementedError for such a request. */
+int mi_sample_truncated(const mi_bf16* logits, int64_t row_stride, const float* temperatures,
+                        const int32_t* top_k, const float* top_p, int64_t* out, int rows, int vocab,
+                        uint64_t seed, uint64_t step, mi_stream stream);
+int mi_sample_truncated_rng(const mi_bf16* logits, int64_t row_stride, const float* temperatures,
+                            const int32_t* top_k, const float* top_p, const uint64_t* rng, int64_t* out,
+                            int rows, int vocab, mi_stream stream);
+
 /* The head GEMM and the sampler in one pass (decode, one GPU: embed_head.py:57-61
  * followed by sampler.py:9-17).  y = x @ W^T as mi_gemm_bf16_packed, and every
  * workgroup also reports the best sampling key of its columns per row - the key

@@ -121,14 +121,16 @@ class DecodeStager:
     a rebuilt table (preemption + re-prefill bumps `table_gen`) - moves into it; otherwise only the
     newly appended block ids are written.  Produces exactly decode_meta(seqs, pad_to=bucket, ...)."""
 
-    def __init__(self, ids, pos, ctx, slots, tables, temps=None):
+    def __init__(self, ids, pos, ctx, slots, tables, temps=None, top_k=None, top_p=None):
         self.ids, self.pos, self.ctx, self.slots, self.tables, self.temps = ids, pos, ctx, slots, tables, temps
+        self.top_k, self.top_p = top_k, top_p
         self.tables[:] = -1
         self._owner = [(-1, -1, 0)] * tables.shape[0]  # (seq_id, table_gen, entries written) per row
 
     def fill(self, seqs: list[Sequence], bucket: int, dummy_block: int) -> None:
         real = len(seqs)
         tables, owner = self.tables, self._owner
+        self.truncates = False  # does any sequence of the step sample with top_k / top_p?
         if real:
             # column-wise: one list per field, one numpy assignment each (per-element numpy stores
             # cost ~0.1 us apiece; a decode step runs this for every sequence)
@@ -142,6 +144,11 @@ class DecodeStager:
             self.slots[:real, 1] = [(n - 1) % bs for n in lens]
             if self.temps is not None:
                 self.temps[:real] = [0.0 if s.greedy else s.temperature for s in seqs]
+            # (written only for a step that truncates, and read only by that step's mi_sample_truncated launch)
+            self.truncates = self.top_k is not None and any(s.truncates for s in seqs)
+            if self.truncates:
+                self.top_k[:real] = [s.top_k for s in seqs]
+                self.top_p[:real] = [s.top_p for s in seqs]
         for i, s in enumerate(seqs):
             table = s.block_table
             nb = len(table)

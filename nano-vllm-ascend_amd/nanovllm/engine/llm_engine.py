@@ -200,6 +200,9 @@ class LLMEngine:
             raise ValueError(f"prompt of {len(prompt)} tokens exceeds max_model_len = {self.scheduler.max_model_len} "
                              "(Config.max_model_len, clamped to the model's max_position_embeddings)")
         seq = Sequence(prompt, sampling_params, request_id=request_id, block_size=self.block_size)
+        if seq.truncates and self.config.tensor_parallel_size > 1:
+            # the ranks hold vocabulary shards and the step record (engine/rpc.py) has no room for the two fields
+            raise NotImplementedError("top_k / top_p sampling runs on one GPU: not with tensor_parallel_size > 1")
         # request preprocessing (the token array built by Sequence, the chained hashes of the prompt's full blocks) runs
         # BEFORE the clock starts: the reference's serving benchmark stamps a request's submission after add_request has
         # returned (bench/serving_bench.py:100-105), i.e. its TTFT excludes add_request as well

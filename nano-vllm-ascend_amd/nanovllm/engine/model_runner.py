@@ -431,9 +431,10 @@ class ModelRunner:
         W = -(-(cfg.max_model_len + 1) // self.block_size)  # a max-length prompt still decodes one token
         self.table_cols = W
         # [ids i64 B][pos i64 B][rng u64 2][temps f32 B][ctx i32 B][src i32 B][slots i32 2B][tables i32 B*W]
+        # [topk i32 B][topp f32 B]
         off, spans = 0, {}
         for name, nbytes in (("ids", 8 * B), ("pos", 8 * B), ("rng", 16), ("temps", 4 * B), ("ctx", 4 * B),
-                             ("src", 4 * B), ("slots", 8 * B), ("tables", 4 * B * W)):
+                             ("src", 4 * B), ("slots", 8 * B), ("tables", 4 * B * W), ("topk", 4 * B), ("topp", 4 * B)):
             spans[name] = (off, nbytes)
             off += (nbytes + 15) // 16 * 16
         self._stage_bytes = off
@@ -447,7 +448,8 @@ class ModelRunner:
             return {"ids": v("ids", torch.int64, (B,)), "pos": v("pos", torch.int64, (B,)),
                     "rng": v("rng", torch.int64, (2,)), "temps": v("temps", torch.float32, (B,)),
                     "ctx": v("ctx", torch.int32, (B,)), "src": v("src", torch.int32, (B,)),
-                    "slots": v("slots", torch.int32, (B, 2)), "tables": v("tables", torch.int32, (B, W))}
+                    "slots": v("slots", torch.int32, (B, 2)), "tables": v("tables", torch.int32, (B, W)),
+                    "topk": v("topk", torch.int32, (B,)), "topp": v("topp", torch.float32, (B,))}
 
         self.dev = views(self.dev_stage)
         # TWO pinned staging buffers (+ token landing buffers and events), used alternately: a step queued
@@ -460,9 +462,11 @@ class ModelRunner:
             self.host_stages.append(buf)
             self.hosts.append(h)
             self.stagers.append(batch_meta.DecodeStager(h["ids"], h["pos"], h["ctx"], h["slots"], h["tables"],
-                                                        h["temps"]))
+                                                        h["temps"], h["topk"], h["topp"]))
         self._flip = 0
         self._src_dirty = [False, False]
+        self._prefill_trunc = None   # (top_k, top_p) on the device for the eager prefill step just staged, if it truncates
+        self._pg_truncates = False   # does the captured prefill step just staged truncate?
         self.tokens_dev = torch.zeros(B, dtype=torch.int64, device=self.device)
         self.tokens_hosts = [torch.zeros(B, dtype=torch.int64, pin_memory=True) for _ in range(2)]
         self.step_events = [torch.cuda.Event() for _ in range(2)]
@@ -481,7 +485,7 @@ class ModelRunner:
         self.prefill_events = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         self._prefill_events_recorded = [False, False]
         # captured prefill steps (capture_prefill_graphs) read their metadata at FIXED addresses: one static device buffer
-        # [ids i64 T][pos i64 T][slots i32 T][cu_q i32 S+1][cu_k i32 S+1][kv_lens i32 S][temps f32 S][rng u64 2][tables i32 S*W]
+        # [ids i64 T][pos i64 T][slots i32 T][cu_q i32 S+1][cu_k i32 S+1][kv_lens i32 S][temps f32 S][rng u64 2][tables i32 S*W][topk i32 S][topp f32 S]
         # for the largest bucket, of which a graph uses the leading T_b / S_b entries; two pinned mirrors, alternating
         t_cap = cfg.max_num_batched_tokens if self.world_size == 1 else min(cfg.max_num_batched_tokens,
                                                                             TP_PREFILL_GRAPH_TOKENS)
@@ -495,7 +499,7 @@ class ModelRunner:
             off, sp = 0, {}
             for name, nb in (("ids", 8 * tmax), ("pos", 8 * tmax), ("slots", 4 * tmax), ("cu_q", 4 * (smax + 1)),
                              ("cu_k", 4 * (smax + 1)), ("kv_lens", 4 * smax), ("temps", 4 * smax), ("rng", 16),
-                             ("tables", 4 * smax * W)):
+                             ("tables", 4 * smax * W), ("topk", 4 * smax), ("topp", 4 * smax)):
                 sp[name] = (off, nb)
                 off += (nb + 15) // 16 * 16
 
@@ -507,7 +511,8 @@ class ModelRunner:
                         "slots": v("slots", torch.int32, (tmax,)), "cu_q": v("cu_q", torch.int32, (smax + 1,)),
                         "cu_k": v("cu_k", torch.int32, (smax + 1,)), "kv_lens": v("kv_lens", torch.int32, (smax,)),
                         "temps": v("temps", torch.float32, (smax,)), "rng": v("rng", torch.int64, (2,)),
-                        "tables": v("tables", torch.int32, (smax, W))}
+                        "tables": v("tables", torch.int32, (smax, W)),
+                        "topk": v("topk", torch.int32, (smax,)), "topp": v("topp", torch.float32, (smax,))}
 
             self.pg_dev_buf = torch.zeros(off, dtype=torch.uint8, device=self.device)
             self.pg_dev = pviews(self.pg_dev_buf)
@@ -565,6 +570,10 @@ class ModelRunner:
         temps = np.fromiter((0.0 if s.greedy else s.temperature for s in seqs), dtype=np.float32, count=len(seqs))
         arrays = (m.input_ids, m.positions, m.slot_mapping, m.cu_seqlens_q, m.cu_seqlens_k, m.kv_lens,
                   np.ascontiguousarray(m.block_tables), temps)
+        truncates = any(s.truncates for s in seqs)
+        if truncates:  # top_k / top_p of the step's rows, for the mi_sample_truncated launch behind its sampler
+            arrays += (np.fromiter((s.top_k for s in seqs), dtype=np.int32, count=len(seqs)),
+                       np.fromiter((s.top_p for s in seqs), dtype=np.float32, count=len(seqs)))
         offs, off = [], 0
         for a in arrays:
             offs.append(off)
@@ -589,6 +598,7 @@ class ModelRunner:
                     context_lens=None, block_tables=dev(6, torch.int32, tuple(m.block_tables.shape)),
                     block_size=self.block_size, kv_lens=dev(5, torch.int32))
         self._prefill_temps = dev(7, torch.float32)
+        self._prefill_trunc = (dev(8, torch.int32), dev(9, torch.float32)) if truncates else None
         return dev(0, torch.int64), dev(1, torch.int64)
 
     def prepare_decode(self, seqs: list[Sequence], bucket: int | None = None):
@@ -606,6 +616,14 @@ class ModelRunner:
         """The temperatures of the prefill step just staged (prepare_prefill uploaded them with the step's metadata)."""
         assert self._prefill_temps.numel() == len(seqs)
         return self._prefill_temps
+
+    def _truncate(self, logits, temps, top_k, top_p, real: int, rng=None) -> None:
+        """One mi_sample_truncated launch behind a step's own token choice: the rows that sample with top_k / top_p get
+        their token from their kept columns, with the keys the step sampled with (`rng`: the device pair staged for it;
+        None: the sampler's seed and the step it has just used); the other rows of tokens_dev are not touched.  Queued
+        on the step's stream in front of the token download, so a lookahead step reads the corrected tokens."""
+        ops.sample_truncated(logits, temps[:real], top_k[:real], top_p[:real], self.sampler.seed, self.sampler.step,
+                             out=self.tokens_dev[:real], rng=rng)
 
     # ------------------------------------------------------------------ graphs
     @torch.inference_mode()
@@ -816,6 +834,10 @@ class ModelRunner:
             h["tables"][:n, :m.block_tables.shape[1]] = m.block_tables
             h["temps"][:n] = [0.0 if s.greedy else s.temperature for s in seqs]
             h["temps"][n:sb] = 0.0
+            self._pg_truncates = any(s.truncates for s in seqs)
+            if self._pg_truncates:
+                h["topk"][:n] = [s.top_k for s in seqs]
+                h["topp"][:n] = [s.top_p for s in seqs]
         else:
             # capture / its warm-up run: sb sequences sharing the tb tokens evenly that store nothing (slots -1) and
             # attend the reserved dummy block (the decode graphs' pad slot) - every kernel runs over mapped memory,
@@ -824,6 +846,7 @@ class ModelRunner:
             h["cu_q"][:sb + 1] = h["cu_k"][:sb + 1] = edges
             h["kv_lens"][:sb] = np.diff(edges)
             h["temps"][:sb] = 0.0
+            self._pg_truncates = False
             h["tables"][:sb] = -1
             h["tables"][:sb, :-(-max(np.diff(edges)) // self.block_size)] = self.config.num_kvcache_blocks - 1
         h["ids"][real_t:tb], h["pos"][real_t:tb], h["slots"][real_t:tb] = 0, 0, -1
@@ -877,6 +900,10 @@ class ModelRunner:
                 self.sampler.step += 1  # the replayed graph sampled with this step (see _fill_decode_stage)
             else:
                 self.sampler(logits, temps, out=self.tokens_dev[:real])
+            if is_prefill and self._prefill_trunc is not None:
+                self._truncate(logits, temps, *self._prefill_trunc, real)
+            elif not is_prefill and self.stagers[self._flip].truncates:
+                self._truncate(logits, temps, self.dev["topk"], self.dev["topp"], real, rng=self.dev["rng"])
             landing = self.tokens_hosts[self._flip]
             landing[:real].copy_(self.tokens_dev[:real], non_blocking=True)
             torch.cuda.current_stream().synchronize()
@@ -913,6 +940,9 @@ class ModelRunner:
         self.graphs[bucket].replay()
         self.sampler.step += 1  # the graph sampled with this step (see _fill_decode_stage)
         if self.rank == 0:
+            if self.stagers[b].truncates:
+                d = self.dev
+                self._truncate(self.graph_logits[bucket], d["temps"], d["topk"], d["topp"], real, rng=d["rng"])
             self._download_tokens(self.tokens_hosts[b], real)
             if self.xgmi is not None:  # the exchange's timeout flag travels with the tokens: no device sync here
                 self.xgmi.status_async(self._xgmi_flag)
@@ -963,6 +993,10 @@ class ModelRunner:
             self.prefill_graph_replays += 1
             self.last_logits = self.prefill_graph_logits[bucket][:real]
             if self.rank == 0:
+                if self._pg_truncates:
+                    d = self.pg_dev
+                    self._truncate(self.prefill_graph_logits[bucket], d["temps"], d["topk"], d["topp"], real,
+                                   rng=d["rng"])
                 self._download_tokens(self.prefill_tokens_hosts[b], real)
                 if self.xgmi is not None:  # the exchange's timeout flag travels with the tokens: no device sync here
                     self.xgmi.status_async(self._xgmi_flag)
@@ -977,6 +1011,8 @@ class ModelRunner:
         logits = self.run_model(input_ids, positions, True, None)
         self.last_logits = logits
         self.sampler(logits, temps, out=self.tokens_dev[:real])
+        if self._prefill_trunc is not None:
+            self._truncate(logits, temps, *self._prefill_trunc, real)
         self.prefill_tokens_hosts[b][:real].copy_(self.tokens_dev[:real], non_blocking=True)
         self.prefill_events[b].record()
         self._steps_run += 1

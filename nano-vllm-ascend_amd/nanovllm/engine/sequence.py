@@ -31,7 +31,7 @@ class Sequence:
 
     __slots__ = ("block_size", "seq_id", "request_id", "status", "token_ids", "last_token", "num_tokens",
                  "num_prompt_tokens", "num_cached_tokens", "block_table", "temperature", "max_tokens",
-                 "ignore_eos", "greedy", "finish_reason", "arrival_time", "first_token_time", "table_gen", "num_prefix_tokens",
+                 "ignore_eos", "greedy", "top_k", "top_p", "truncates", "finish_reason", "arrival_time", "first_token_time", "table_gen", "num_prefix_tokens",
                  "token_pending", "_prompt_q", "_prompt_hashes")
 
     def __init__(self, token_ids: list[int], sampling_params: SamplingParams | None = None,
@@ -50,6 +50,9 @@ class Sequence:
         self.max_tokens = sp.max_tokens
         self.ignore_eos = sp.ignore_eos
         self.greedy = getattr(sp, "greedy", False)
+        self.top_k = getattr(sp, "top_k", 0)
+        self.top_p = getattr(sp, "top_p", 1.0)
+        self.truncates = self.top_k > 0 or self.top_p < 1.0  # the step needs mi_sample_truncated behind its pick
         self.finish_reason = None
         self.arrival_time = 0.0
         self.first_token_time = 0.0
@@ -190,6 +193,7 @@ class Sequence:
         s.num_tokens, s.num_prompt_tokens, s.num_cached_tokens = num_tokens, num_prompt, num_cached
         s.temperature = struct.unpack("<d", struct.pack("<q", tbits))[0]
         s.greedy = bool(greedy)
+        s.top_k, s.top_p, s.truncates = 0, 1.0, False  # not in the record: add_request refuses them under TP
         s.table_gen, s.num_prefix_tokens = table_gen, num_prefix
         s.max_tokens, s.ignore_eos, s.finish_reason = 0, True, None
         s.arrival_time = s.first_token_time = 0.0

@@ -1001,6 +1001,38 @@ def sample(logits, temperatures, seed: int, step: int, out=None) -> torch.Tensor
     return out
 
 
+def sample_truncated(logits, temperatures, top_k, top_p, seed: int, step: int, out=None, rng=None) -> torch.Tensor:
+    """Top-k / top-p sampling: sample(logits, temperatures, seed, step) over the columns each row keeps (top_k [rows]
+    int32, <= 0 off; top_p [rows] float32, >= 1 off; semantics in include/mi355_nanovllm.h).  Rows with both off are NOT
+    written: they keep what `out` holds (a new `out` holds -1 there).  `rng`: the device pair {seed, step} (int64 [2])
+    to read instead of the two scalars."""
+    require_gpu(logits, temperatures, top_k, top_p)
+    _bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    assert temperatures.dtype == torch.float32 and temperatures.is_contiguous()
+    assert top_k.dtype == torch.int32 and top_k.is_contiguous() and top_p.dtype == torch.float32 and top_p.is_contiguous()
+    rows, vocab = temperatures.numel(), logits.shape[1]
+    assert logits.shape[0] >= rows and top_k.numel() == rows and top_p.numel() == rows
+    if out is None:
+        out = torch.full((rows,), -1, dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= rows
+    if rng is not None:
+        require_gpu(rng)
+        assert rng.dtype == torch.int64 and rng.numel() == 2
+        check(
+            lib.mi_sample_truncated_rng(ptr(logits), logits.stride(0), ptr(temperatures), ptr(top_k), ptr(top_p),
+                                        ptr(rng), ptr(out), rows, vocab, stream()),
+            "mi_sample_truncated_rng",
+        )
+        return out
+    check(
+        lib.mi_sample_truncated(ptr(logits), logits.stride(0), ptr(temperatures), ptr(top_k), ptr(top_p), ptr(out),
+                                rows, vocab, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFFFFFFFFFF, stream()),
+        "mi_sample_truncated",
+    )
+    return out
+
+
 def gemm_packed_pick(x, w_packed, temperatures, rng, out_tokens, logits=None, candidates=None, col_offset: int = 0,
                      pairs_out=None):
     """logits = x @ w.T (as gemm_packed) and, in the same pass, the sampler's token per row
