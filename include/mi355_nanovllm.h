@@ -664,6 +664,26 @@ int mi_gemm_fp8w_packed(const mi_bf16* x, const uint8_t* w_packed, const float* 
 int mi_gemm_fp8w_packed_splitk(const mi_bf16* x, const uint8_t* w_packed, const float* scale,
                                float* partials, int M, int N, int K, int ksplit, mi_stream stream);
 
+/* ---- int4 (group-128) weights, bf16 activations -----------------------------
+ * No reference semantics exist.  y = x @ w_d^T with w_d[n][k] = (q[n][k] - 8) * s[n][k / 128]: q a nibble 0..15 and
+ * s a bf16 scale per row and group of 128 consecutive k whose significand has four bits (its low four mantissa bits
+ * are zero), so that every w_d is EXACT in bf16 and a bf16 GEMM over w_d computes the same model.  The nibbles are
+ * expanded to bf16 in registers and multiplied on the bf16 MFMA; the only error is fp32 summation order.
+ * N % 16 == 0 and K % 128 == 0 (MI_EUNSUPPORTED otherwise, checked before any launch).
+ * mi_pack_weight_int4: q [N][K] row-major, one code per byte (the low nibble counts), scale [N][K / 128] ->
+ *   w_packed     [N/16][K/128][64 lanes][16 bytes]: lane (g = lane / 16, r = lane % 16) holds row 16 tn + r; dword s of
+ *                its 16 bytes = the codes of k = 128 tk + 32 s + 8 g + e, code e at bits 4 e       (N * K / 2 bytes)
+ *   scale_packed [N/16][K/128][16] bf16, rows of the tile in order                               (N * K / 64 bytes)
+ * mi_gemm_int4w_packed: epilogue 0: y [M][N]; 1: y [M][N/2] = silu(gate) * up as mi_gemm_bf16_packed (N % 32 == 0).
+ * mi_gemm_int4w_packed_splitk: fp32 partials [ksplit][M][N] for mi_add_rmsnorm_splitk; K % (128 * ksplit) == 0.
+ * M up to 512 rows (chunks of 64), every pointer 16-byte aligned. */
+int mi_pack_weight_int4(const uint8_t* q, const mi_bf16* scale, uint8_t* w_packed, mi_bf16* scale_packed,
+                        int N, int K, mi_stream stream);
+int mi_gemm_int4w_packed(const mi_bf16* x, const uint8_t* w_packed, const mi_bf16* scale_packed, mi_bf16* y,
+                         int M, int N, int K, int epilogue, mi_stream stream);
+int mi_gemm_int4w_packed_splitk(const mi_bf16* x, const uint8_t* w_packed, const mi_bf16* scale_packed,
+                                float* partials, int M, int N, int K, int ksplit, mi_stream stream);
+
 /* ---- mixture of experts (reference: models/qwen3_moe.py:125-185, BASELINE.json configs[3]) -------------
  * Qwen3MoeSparseMoeBlock.forward as five launches over expert-sorted (token, expert) pairs; P = n_tokens * top_k.
  * The reference loops over the selected experts in Python with three library GEMMs each (:171-184).

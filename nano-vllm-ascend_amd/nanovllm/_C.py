@@ -174,6 +174,9 @@ _SIGNATURES = {
     "mi_pack_weight_fp8": (c_int, [_p, _p, c_int, c_int, _p]),
     "mi_gemm_fp8w_packed": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, _p]),
     "mi_gemm_fp8w_packed_splitk": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, _p]),
+    "mi_pack_weight_int4": (c_int, [_p, _p, _p, _p, c_int, c_int, _p]),
+    "mi_gemm_int4w_packed": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, _p]),
+    "mi_gemm_int4w_packed_splitk": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, _p]),
     "mi_moe_route": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p]),
     "mi_moe_sort": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, _p]),
     "mi_moe_gate_up": (c_int, [_p, _p, _p, _p, _p, c_int, c_int, c_int, _p]),

@@ -47,7 +47,9 @@ class Config:
     synthetic_seed: int = 0
     decode_lookahead: bool = True  # one GPU: queue decode step k+1 before step k's tokens reach the host
     sampling_seed: int | None = None  # seed of the temperature sampler; None: drawn from os.urandom per engine
-    quantization: str | None = None  # "fp8": e4m3 weights + per-row scales for the decode GEMMs (no reference counterpart)
+    # "fp8": e4m3 weights + per-row scales for the decode GEMMs; "int4": nibbles + a scale per group of 128 k for the
+    # dense projections' decode GEMMs, the head and MoE experts stay bf16 (no reference counterpart)
+    quantization: str | None = None
     kv_cache_dtype: str = "bf16"  # "fp8": e4m3 KV cache, one power-of-two scale per (token, kv head) (no reference counterpart)
     prefix_aware_prefill: bool = True  # skip the tokens of cache-hit prefix blocks in prefill (False: recompute, as the reference)
     prefill_graphs: bool = True  # prefill steps of up to 4 sequences / 4096 tokens replay bucketed hipGraphs (engine/model_runner.py)
@@ -61,7 +63,7 @@ class Config:
         assert self.kvcache_block_size % 16 == 0
         assert 1 <= self.tensor_parallel_size <= 8
         assert self.graph_mode in {m.value for m in GraphMode}, self.graph_mode
-        assert self.quantization in (None, "fp8"), self.quantization
+        assert self.quantization in (None, "fp8", "int4"), self.quantization
         assert self.kv_cache_dtype in ("bf16", "fp8"), self.kv_cache_dtype
         if self.sampling_seed is None:
             self.sampling_seed = int.from_bytes(os.urandom(8), "little") >> 1

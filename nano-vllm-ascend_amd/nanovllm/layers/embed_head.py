@@ -47,7 +47,7 @@ class ParallelLMHead(VocabParallelEmbedding):
         self.weight_packed = None
 
     def pack(self) -> None:
-        self.weight_packed = pack_for_decode(self.weight.data, self.weight_packed)
+        self.weight_packed = pack_for_decode(self.weight.data, self.weight_packed, head=True)
 
     def local_logits(self, x: torch.Tensor) -> torch.Tensor:
         """This rank's vocabulary shard of the logits (kernels only: what a decode graph captures)."""

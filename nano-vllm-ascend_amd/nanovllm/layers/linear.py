@@ -42,10 +42,10 @@ def linear_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | N
     rows = x.numel() // x.shape[-1]
     n, k = weight.shape
     tile_ok = tile_gemm_takes(rows, n, k)
-    tileable = tile_ok and not isinstance(packed, ops.Fp8Weight)
+    tileable = tile_ok and not isinstance(packed, ops.QUANT_WEIGHTS)
 
     def streamed(xr: torch.Tensor) -> torch.Tensor:
-        if isinstance(packed, ops.Fp8Weight):  # the fp8 GEMM has no bias operand
+        if isinstance(packed, ops.QUANT_WEIGHTS):  # the fp8 / int4 GEMMs have no bias operand
             y = ops.gemm_packed(xr, packed)
             return y if bias is None else y.add_(bias)
         if packed is not None:
@@ -79,17 +79,24 @@ _QUANTIZATION: str | None = None  # set by the runner from Config.quantization b
 
 
 def set_weight_quantization(mode: str | None) -> None:
-    assert mode in (None, "fp8"), mode
+    assert mode in (None, "fp8", "int4"), mode
     global _QUANTIZATION
     _QUANTIZATION = mode
 
 
-def pack_for_decode(weight: torch.Tensor, previous):
+def pack_for_decode(weight: torch.Tensor, previous, head: bool = False):
     """The decode-GEMM copy of a (sharded) weight: fragment-native bf16, or - Config.quantization == "fp8" -
-    fragment-native e4m3 + per-row scale.  In fp8 mode the bf16 parameter itself is replaced by the
-    dequantised values, so the prefill (the bf16 tile GEMM) and anything tied to it see the same model."""
+    fragment-native e4m3 + per-row scale, or - "int4" - nibbles + one scale per group of 128 k (N % 16 == 0 and
+    K % 128 == 0; not the lm head (`head`), which 4-bit checkpoints keep in bf16 too).  In both quantised modes the
+    bf16 parameter itself is replaced by the dequantised values, so the prefill (the bf16 tile GEMM) and anything
+    tied to it see the same model."""
     if not can_pack(weight):
         return None
+    if _QUANTIZATION == "int4" and not head and weight.shape[1] % ops.INT4_GROUP == 0:
+        q, scale = ops.quantize_int4(weight)
+        packed = ops.pack_weight_int4((q, scale), previous if isinstance(previous, ops.Int4Weight) else None)
+        weight.copy_(ops.dequantize_int4(q, scale))
+        return packed
     if _QUANTIZATION == "fp8" and weight.shape[1] % 64 == 0:
         packed = ops.pack_weight_fp8(weight, previous if isinstance(previous, ops.Fp8Weight) else None)
         q, scale = ops.quantize_fp8(weight)
@@ -198,7 +205,7 @@ class RowParallelLinear(LinearBase):
         w = self.weight.data
         # complete rows from four-feature workgroups pay off while N is too small to fill the CUs with
         # 16-feature row tiles (N = 1024: 64 tiles); at N = 5120 the packed kernel is 1.6-2.2x faster
-        if self.tp_size > 1 and w.is_cuda and not isinstance(self.weight_packed, ops.Fp8Weight) \
+        if self.tp_size > 1 and w.is_cuda and not isinstance(self.weight_packed, ops.QUANT_WEIGHTS) \
                 and w.shape[0] % 4 == 0 and w.shape[1] % 32 == 0 and w.shape[0] // 16 < 256:
             self.weight_rows4 = ops.pack_weight_rows4(w, self.weight_rows4)
         else:

@@ -88,7 +88,7 @@ class Qwen3Attention(nn.Module):
         ctx, proj = get_context(), self.qkv_proj
         return (self.fused and ctx.is_prefill and self.attn.k_cache.numel() > 0 and self.attn.fusable and x.is_cuda
                 and x.dim() == 2 and ctx.slot_mapping is not None and ctx.slot_mapping.dim() == 1
-                and not isinstance(getattr(proj, "weight_packed", None), ops.Fp8Weight)
+                and not isinstance(getattr(proj, "weight_packed", None), ops.QUANT_WEIGHTS)
                 and proj.weight.dtype == torch.bfloat16 and proj.weight.shape[1] % 64 == 0
                 and ops.qkv_store_takes(x.shape[0], proj.weight.shape[0], self.head_dim, ctx.block_size)
                 and os.environ.get("MI355_PREFILL_FUSED_Q", "1") != "0" and os.environ.get("MI355_QKV_STORE", "0") == "1")
@@ -200,7 +200,7 @@ class Qwen3MLP(nn.Module):
         gu = self.gate_up_proj
         rows = x.numel() // x.shape[-1]
         if (ops.prefers_tile(rows, gu.weight.shape[0]) and gu.bias is None and x.is_cuda and gu.weight.shape[1] % 64 == 0
-                and (gu.weight.shape[0] // 2) % 128 == 0 and not isinstance(gu.weight_packed, ops.Fp8Weight)):
+                and (gu.weight.shape[0] // 2) % 128 == 0 and not isinstance(gu.weight_packed, ops.QUANT_WEIGHTS)):
             # prefill-sized: SiluAndMul is the tile GEMM's epilogue (the reference's three roundings; the
             # 2 x intermediate wide gate_up output never exists in memory)
             shape = x.shape
@@ -314,7 +314,7 @@ class Qwen3Model(nn.Module):
             if hasattr(mlp, "experts"):
                 return False
             lins = (attn.qkv_proj, attn.o_proj, mlp.gate_up_proj, mlp.down_proj)
-            if any(isinstance(l.weight_packed, ops.Fp8Weight) for l in lins):
+            if any(isinstance(l.weight_packed, ops.QUANT_WEIGHTS) for l in lins):
                 return False
         l0 = self.layers[0]
         return ops.chain5_takes(rows, hidden, (l0.self_attn.o_proj.weight.shape[1], l0.mlp.down_proj.weight.shape[1]))
@@ -397,7 +397,7 @@ class Qwen3Model(nn.Module):
             128-tile MFMA kernel on the weight as stored (ops.prefers_tile)"""
             w = lin.weight
             if (ops.prefers_tile(rows, w.shape[0]) and w.shape[1] % 64 == 0
-                    and not isinstance(lin.weight_packed, ops.Fp8Weight)
+                    and not isinstance(lin.weight_packed, ops.QUANT_WEIGHTS)
                     and (not silu_mul or (w.shape[0] // 2) % 128 == 0)):
                 return ops.gemm_tile(x, w, silu_mul=silu_mul)
             return ops.gemm_packed(x, lin.weight_packed, silu_mul=silu_mul)

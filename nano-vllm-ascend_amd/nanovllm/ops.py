@@ -772,6 +772,58 @@ def pack_weight_fp8(w, out: Fp8Weight | None = None) -> Fp8Weight:
     return out
 
 
+class Int4Weight:
+    """int4 (group-128) copy of a [N, K] weight for mi_gemm_int4w_packed: `data` uint8 [N, K / 2], the nibbles in MFMA
+    fragment order, `scale` bf16 [N / 16, K / 128, 16] (mi_pack_weight_int4)."""
+    __slots__ = ("data", "scale", "shape")
+
+    def __init__(self, data: torch.Tensor, scale: torch.Tensor, shape):
+        self.data, self.scale, self.shape = data, scale, tuple(shape)
+
+
+QUANT_WEIGHTS = (Fp8Weight, Int4Weight)  # decode copies that only the weight-streaming GEMMs read
+INT4_GROUP = 128
+
+
+def quantize_int4(w: torch.Tensor):
+    """Symmetric 4-bit quantisation in groups of 128 consecutive k of a row: (codes uint8 [N, K] in 1..15 (a nibble
+    each, 8 = zero), scale bf16 [N, K / 128]).  The scale is the smallest value >= max|w| / 7 of the group whose
+    significand has FOUR bits (at most 12.5 % above max|w| / 7), 1 for an all-zero group: (q - 8) * scale then has at
+    most eight significant bits - the dequantised weight is exact in bf16.  Plain torch, any device."""
+    n, k = w.shape
+    assert k % INT4_GROUP == 0
+    wd = w.double().reshape(n, k // INT4_GROUP, INT4_GROUP)  # fp64: the quotient's rounding cannot reach a 4-bit step
+    m, e = torch.frexp(wd.abs().amax(dim=-1) / 7)            # m in [0.5, 1): m * 16 in [8, 16)
+    scale = torch.ldexp(torch.ceil(m * 16) / 16, e)
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    q = torch.round(wd / scale[..., None]).clamp_(-8, 7) + 8  # round half to even
+    return q.reshape(n, k).to(torch.uint8), scale.to(_BF16)
+
+
+def dequantize_int4(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] = (q - 8) * scale, exact for a four-bit-significand scale."""
+    n, k = q.shape
+    w = (q.float() - 8).reshape(n, k // INT4_GROUP, INT4_GROUP) * scale.float()[..., None]
+    return w.reshape(n, k).to(_BF16)
+
+
+def pack_weight_int4(w, out: Int4Weight | None = None) -> Int4Weight:
+    """Quantise a bf16 [N, K] weight - or take caller-supplied (codes, scale) as quantize_int4 returns them - and lay
+    it out for mi_gemm_int4w_packed (refreshes `out` in place)."""
+    q, scale = w if isinstance(w, tuple) else quantize_int4(w)
+    require_gpu(q, scale)
+    n, k = q.shape
+    assert q.dtype == torch.uint8 and scale.dtype == _BF16 and n % 16 == 0 and k % INT4_GROUP == 0
+    assert scale.shape == (n, k // INT4_GROUP)
+    q, scale = q.contiguous(), scale.contiguous()
+    if out is None or out.shape != (n, k) or out.data.device != q.device:
+        out = Int4Weight(torch.empty((n, k // 2), dtype=torch.uint8, device=q.device),
+                         torch.empty((n // 16, k // INT4_GROUP, 16), dtype=_BF16, device=q.device), (n, k))
+    check(lib.mi_pack_weight_int4(ptr(q), ptr(scale), ptr(out.data), ptr(out.scale), n, k, stream()),
+          "mi_pack_weight_int4")
+    return out
+
+
 def gemm_packed(x, w_packed, bias=None, out=None, silu_mul: bool = False) -> torch.Tensor:
     require_gpu(x, bias)
     _bf16(x, bias)
@@ -787,6 +839,11 @@ def gemm_packed(x, w_packed, bias=None, out=None, silu_mul: bool = False) -> tor
         assert bias is None
         check(lib.mi_gemm_fp8w_packed(ptr(x), ptr(w_packed.data), ptr(w_packed.scale), ptr(out), M, N, K,
                                       int(silu_mul), stream()), "mi_gemm_fp8w_packed")
+        return out
+    if isinstance(w_packed, Int4Weight):
+        assert bias is None
+        check(lib.mi_gemm_int4w_packed(ptr(x), ptr(w_packed.data), ptr(w_packed.scale), ptr(out), M, N, K,
+                                       int(silu_mul), stream()), "mi_gemm_int4w_packed")
         return out
     require_gpu(w_packed)
     _bf16(w_packed)
@@ -834,6 +891,10 @@ def gemm_packed_splitk(x, w_packed, ksplit: int, out=None) -> torch.Tensor:
     if isinstance(w_packed, Fp8Weight):
         check(lib.mi_gemm_fp8w_packed_splitk(ptr(x), ptr(w_packed.data), ptr(w_packed.scale), ptr(out), M, N, K,
                                              ksplit, stream()), "mi_gemm_fp8w_packed_splitk")
+        return out
+    if isinstance(w_packed, Int4Weight):
+        check(lib.mi_gemm_int4w_packed_splitk(ptr(x), ptr(w_packed.data), ptr(w_packed.scale), ptr(out), M, N, K,
+                                              ksplit, stream()), "mi_gemm_int4w_packed_splitk")
         return out
     require_gpu(w_packed)
     _bf16(w_packed)

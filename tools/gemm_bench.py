@@ -2,7 +2,8 @@
 (16384 tokens x the four Qwen3-0.6B projections) and a few others; every schedule variant of
 mi_gemm_bf16_ex.  Timed as hipGraph replays of REPS back-to-back launches on random data (the guide's rule 25:
 zero-filled operands clock higher).  (Round 4's timing-only variants - no stores - went with that round's EXPERIMENTS=1
-build flavour; their numbers are in profiles/r04_gemm_ablation.txt.)  Usage: python tools/gemm_bench.py [out.json]"""
+build flavour; their numbers are in profiles/r04_gemm_ablation.txt.)  Usage: python tools/gemm_bench.py [out.json]
+GEMM_DECODE=1: the weight-streaming decode GEMMs instead - bf16-packed, fp8 and int4 weights at 1, 8 and 32 rows."""
 import json
 import os
 import sys
@@ -36,8 +37,52 @@ def timed(fn, reps=REPS, rounds=5):
     return best  # us per launch
 
 
+def decode_rows():
+    """us per launch of the decode GEMMs by weight format.  One graph replay walks enough copies of the weight (512 MiB
+    of each format, at most 256 copies) that no launch finds its weight in L2 / the Infinity Cache, as in a decode step,
+    where a layer's weights come round once per step."""
+    rows = []
+    for hidden, inter, qkv, attn in ((1024, 3072, 4096, 2048), (4096, 12288, 6144, 4096)):  # Qwen3-0.6B, Qwen3-8B widths
+        for N, K, label, silu in ((qkv, hidden, "qkv", False), (hidden, attn, "o", False),
+                                  (2 * inter, hidden, "gate_up+silu", True), (hidden, inter, "down", False)):
+            g = torch.Generator().manual_seed(N + K)
+            w = (torch.randn(N, K, generator=g) * 0.02).bfloat16().to(DEV)
+            q4, s4 = ops.quantize_int4(w)
+            first = {"bf16": ops.pack_weight(w), "fp8": ops.pack_weight_fp8(w), "int4": ops.pack_weight_int4((q4, s4))}
+            del q4, s4
+            for fmt, wp in first.items():
+                nbytes = N * K * {"bf16": 2, "fp8": 1, "int4": 0.5}[fmt]
+                n = int(min(256, -(-(512 << 20) // nbytes)))
+                if fmt == "bf16":
+                    copies = [wp] + [wp.clone() for _ in range(n - 1)]
+                else:
+                    copies = [wp] + [type(wp)(wp.data.clone(), wp.scale.clone(), wp.shape) for _ in range(n - 1)]
+                for M in (1, 8, 32):
+                    x = torch.randn(M, K, generator=g).bfloat16().to(DEV)
+                    y = torch.empty(M, N // 2 if silu else N, dtype=torch.bfloat16, device=DEV)
+
+                    def walk():
+                        for c in copies:
+                            ops.gemm_packed(x, c, out=y, silu_mul=silu)
+
+                    t = timed(walk, reps=max(1, 1024 // n)) / n  # ~1000 launches per timed replay
+                    row = {"label": label, "N": N, "K": K, "rows": M, "format": fmt, "us": round(t, 2),
+                           "weight_GBps": round(nbytes / t / 1e3, 1)}
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+                del copies
+            del first
+    return rows
+
+
 def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else None
+    if os.environ.get("GEMM_DECODE"):
+        rows = decode_rows()
+        if out_path:
+            with open(out_path, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     shapes = [  # (M, N, K, label)
         (16384, 4096, 1024, "qkv"), (16384, 1024, 2048, "o_proj"), (16384, 6144, 1024, "gate_up"),
         (16384, 1024, 3072, "down"), (4096, 4096, 1024, "qkv@4k"), (1024, 4096, 1024, "qkv@1k"),
